@@ -1,30 +1,35 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/sec of the PGBART hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one ``PGBART.astep`` (a batch of 10% of the m trees re-sampled by particle Gibbs) on the
 configuration BASELINE.json's metric is quoted on: n=100k, p=50, m=200 trees, 40 particles, Gaussian
 likelihood (cfg2), synthetic data resident in HBM.  ``value`` times the step method itself -- the call
 ``pm.sample`` makes: sum_trees back on the host, the step's trees exported, stats encoded, history
-published (round-2 VERDICT: the honest answer to "PGBART.astep on one MI355X").  The device-resident rate
-(``pgb_step_async``: no host outputs) is reported beside it as ``resident_path``.
+published (round-2 VERDICT: the honest answer to "PGBART.astep on one MI355X").  With ``--full`` the
+device-resident rate (``pgb_step_async``: no host outputs) is reported beside it as ``resident_path``.
 
 N > 1: ``python bench.py --gpus N`` launches its own N ranks (``torch.distributed.run``, one process
 per GPU, RCCL) BEFORE anything touches a GPU; launched under ``torch.distributed.run`` by somebody
 else (RANK set) it is one of those ranks.  N independent chains run one per GPU (weak scaling, no
-data-path collective); the draws are gathered over RCCL after the timed region.  Rank 0 prints ONE
-JSON line.
+data-path collective); with ``--full`` the draws are gathered over RCCL after the timed region.  Rank 0
+prints ONE JSON line.
 
 Protocol (steady state): burn in ``--burnin`` asteps with tune=1 (default 100 = 10 sweeps
-over the m trees), switch to tune=0, W untimed warm-up asteps, then blocks of EXACTLY K asteps, each
-bracketed by barrier + synchronize, until at least ``--min-seconds`` of GPU time have been timed (or
-``--repeats`` blocks when given); ``value`` is the median block (min / max alongside).  Further legs at
-N=1: ``resident_path``, ``tune1``, the per-kernel profile behind ``roofline`` / ``roofline_kernels``, 4
-chains on the one GPU -- and the other single-GPU configurations of BASELINE.json, cfg4 (Bernoulli-probit,
-n=1M) and cfg5 (K=4 softmax, n=250k), each with its own value, dominant-kernel roofline and row-pass HBM
-roofline from measured bytes, under ``workloads``.  ALL GPU legs run first, back to back (the GPU is held
-for ~30 s contiguously); the CPU baselines (cfg2: 1 core and 8 chains on 8 cores; cfg4 / cfg5: a bounded
+over the m trees), switch to tune=0, W untimed warm-up asteps, then ``--repeats`` blocks (default 1) of
+EXACTLY K asteps, each bracketed by barrier + synchronize (``--repeats 0``: blocks until at least
+``--min-seconds`` of GPU time have been timed); ``value`` is the median block (min / max alongside) and
+``ms_per_step`` its milliseconds per astep.  ``--dump-outputs DIR`` then writes what the last timed astep
+handed its caller (sum_trees, the variable-inclusion counts, the trees of the step) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run stops there.  ``--full`` adds the further legs at N=1: ``resident_path``, ``tune1``, the
+per-kernel profile behind ``roofline`` / ``roofline_kernels``, 4 chains on the one GPU -- and the other
+single-GPU configurations of BASELINE.json, cfg4 (Bernoulli-probit, n=1M) and cfg5 (K=4 softmax, n=250k),
+each with its own value, dominant-kernel roofline and row-pass HBM roofline from measured bytes, under
+``workloads``; at N > 1 the end-of-run gather.  ALL GPU legs run first, back to back (the GPU is held for
+~30 s contiguously); the CPU baselines (cfg2: 1 core and 8 chains on 8 cores; cfg4 / cfg5: a bounded
 sample) follow, each with a GPU rate at the SAME chain age beside it (``matched_age``).  The line ENDS with
 a compact ``summary`` object that repeats every headline figure (a log tail keeps it); the prose that
 explains the fields is profiles/BENCH_NOTES.md.
@@ -64,10 +69,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed blocks of --steps asteps; value = median.  0 (default): as many as --min-seconds needs")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of --steps asteps; value = median.  0: as many as --min-seconds needs")
     ap.add_argument("--min-seconds", type=float, default=5.0,
-                    help="GPU time the headline's timed blocks cover at least (also of each workload leg)")
+                    help="GPU time the timed blocks of a workload leg (and of the headline at --repeats 0) cover at least")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every further leg: resident path, tune=1, per-kernel roofline, 4 chains, the cfg4 / "
+                         "cfg5 workloads, the CPU baselines, the end-of-run gather at N > 1 (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed astep returned as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--burnin", type=int, default=100,
                     help="tune=1 asteps before anything is timed (100 = 10 sweeps at the default batch)")
     ap.add_argument("--n", type=int, default=100_000)
@@ -364,24 +374,28 @@ def resident_blocks(ss, tn, steps, repeats, barrier):
     return out
 
 
-def astep_blocks(step, steps, repeats, barrier, min_seconds=0.0, agree=None, max_blocks=400):
+def astep_blocks(step, steps, repeats, barrier, min_seconds=0.0, agree=None, max_blocks=400, last=None):
     """Blocks of exactly ``steps`` calls of ``step.astep`` (the call PyMC makes), each bracketed by
     barrier + synchronize.  ``repeats`` > 0: that many blocks.  Otherwise blocks are added until
-    ``min_seconds`` are covered; ``agree`` (max over ranks of a float) keeps every rank on the same count."""
+    ``min_seconds`` are covered; ``agree`` (max over ranks of a float) keeps every rank on the same count.
+    ``last``: a list that receives what the last astep returned."""
     out = []
     a = dict(step.counters)
 
     def one():
         nonlocal a
+        r = None
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step.astep(None)
+            r = step.astep(None)
         barrier()
         el = time.perf_counter() - t0
         b = dict(step.counters)
         out.append((el, {key: b[key] - a[key] for key in b}))
         a = b
+        if last is not None:
+            last[:] = [r]
         return el
 
     if repeats > 0:
@@ -394,6 +408,35 @@ def astep_blocks(step, steps, repeats, barrier, min_seconds=0.0, agree=None, max
     for _ in range(max(4, min(more, max_blocks - 1))):
         one()
     return out
+
+
+DUMP_LIMIT = 64 << 20  # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(path, res, step):
+    """``--dump-outputs``: what one ``PGBART.astep`` returned to its caller, as float64 ``path/<name>.npy`` files --
+    ``sum_trees``, the decoded ``variable_inclusion`` counts and every field of the trees the step exported into the
+    history (a tune=0 step).  Over ``DUMP_LIMIT`` bytes, ``sum_trees`` is cut to a fixed seeded sample of its entries
+    (flat indices in ``sum_trees_index.npy``)."""
+    from pymc_bart_amd.trees import _HISTORY_FIELDS
+    from pymc_bart_amd.utils import _decode_vi
+
+    sum_trees, stats = res
+    out = {"variable_inclusion": np.asarray(_decode_vi(stats[0]["variable_inclusion"], step.num_variates), np.float64)}
+    batches = step.history[1]
+    if not stats[0]["tune"] and len(batches):
+        for f in _HISTORY_FIELDS:
+            out[f"trees_{f}"] = np.asarray(getattr(batches[-1], f), np.float64)
+    mu = np.asarray(sum_trees, np.float64)
+    free = DUMP_LIMIT - sum(a.nbytes for a in out.values()) - 128 * (len(out) + 2)  # (128 B: an .npy header)
+    if mu.nbytes > free:
+        room = free // 16  # entries: 8 B of value + 8 B of index each
+        idx = np.sort(np.random.default_rng(3415).choice(mu.size, size=int(room), replace=False))
+        out["sum_trees_index"], mu = idx.astype(np.float64), mu.reshape(-1)[idx]
+    out["sum_trees"] = mu
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def kernel_profile(s, tune, steps):
@@ -524,6 +567,9 @@ def main():
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} != WORLD_SIZE {world}")
     dry = args.dry_run
+    if args.dump_outputs and args.chains_per_gpu > 1:
+        raise SystemExit("bench.py: --dump-outputs needs the PGBART.astep headline (--chains-per-gpu 1); "
+                         "the resident path hands no outputs to a caller")
     if not dry and torch.cuda.device_count() < max(1, local_rank + 1):
         raise SystemExit(f"bench.py: rank {rank} has no GPU {local_rank} "
                          f"({torch.cuda.device_count()} visible); there is no CPU fallback")
@@ -651,11 +697,14 @@ def main():
     #      chain).  With several chains per GPU the host-synchronous astep cannot overlap them: there the
     #      headline stays the resident path, as before.
     multi = args.chains_per_gpu > 1
+    last = []
     if multi:
         blocks = resident_blocks(samplers, tune, args.steps, max(1, args.repeats or 5), barrier)
     else:
         blocks = astep_blocks(step, args.steps, args.repeats, barrier, args.min_seconds,
-                              agree=lambda v: allreduce([v], "MAX")[0])
+                              agree=lambda v: allreduce([v], "MAX")[0], last=last)
+    if args.dump_outputs and rank == 0 and not dry:
+        dump_outputs(args.dump_outputs, last[0], step)
     agg = aggregate(blocks)
     (dt_med, u_med), v_min, v_max = median_block(agg)
     per_rank_ms = None
@@ -712,7 +761,7 @@ def main():
             n, line["rows_touched_per_tree"], K=K_out) * u_med["tree_updates"] / dt_med / 1e9
 
     # ---- the device-resident path (no host outputs): what round 1 / 2 quoted as the headline
-    if not multi and not args.no_extras:
+    if args.full and not multi and not args.no_extras:
         (el_r, u_r), r_min, r_max = median_block(aggregate(resident_blocks(samplers, tune, args.steps, 5, barrier)))
         if not dry:
             line["resident_path"] = {
@@ -723,7 +772,7 @@ def main():
             }
 
     # ---- roofline of the dominant kernel + per-kernel shares: a further block with events attached
-    if not dry and not args.no_roofline and rank == 0:
+    if args.full and not dry and not args.no_roofline and rank == 0:
         line.update(rooflines(wname, w, X.shape, kernel_profile(s, tune, args.steps), args.response, default_cfg))
         if line.get("roofline"):
             # SURVEY.md 8(d)'s own definition, over the WALL clock of the timed asteps (host outputs and all):
@@ -731,7 +780,7 @@ def main():
             line["roofline"]["whole_step_frac"] = line["algorithmic_GBps_whole_step"] / HBM_PEAK_GBS
 
     # ---- tune=1 block (reported separately: SURVEY.md 8d)
-    if solo and not args.no_extras and not tune:
+    if args.full and solo and not args.no_extras and not tune:
         run_all(samplers, True, 2)
         (el_t, u_t), t_min, t_max = median_block(resident_blocks(samplers, True, args.steps, 3, barrier))
         line["tune1"] = {"value": u_t["particle_steps"] / el_t, "unit": "particle-steps/s", "path": "resident",
@@ -749,11 +798,11 @@ def main():
     # ---- end-of-run gather (the only collective; outside the timed region): what a user's run hands to rank 0 --
     #      `--gather-draws` kept draws of this chain (100 x n doubles = 80 MB per rank at cfg2), its tree history as
     #      packed records and its variable-inclusion stats -- through chains.gather_chains itself
-    if dist is not None:
+    if args.full and dist is not None:
         line.update(end_of_run_gather(step, dist, rank, world, dry, args, seed, barrier))
 
     # ---- informational: PyMC's default of 4 chains, run concurrently on ONE GPU (never the headline)
-    if solo and not args.no_multichain:
+    if args.full and solo and not args.no_multichain:
         ss4 = samplers + extra_chains(3, 1)
         run_all(ss4[1:], True, min(args.burnin, 20))
         run_all(ss4, False, 2)
@@ -767,7 +816,8 @@ def main():
     # ---- the other single-GPU configurations of BASELINE.json, under the same clock: GPU legs only here,
     #      back to back with the headline's; their CPU samples follow after every GPU leg of the run
     pending_cpu = []
-    if solo and args.workload == "cfg2" and default_cfg and not args.no_extras and not args.no_workloads and not tune:
+    if (args.full and solo and args.workload == "cfg2" and default_cfg and not args.no_extras and not args.no_workloads
+            and not tune):
         del samplers, s
         step.sampler = None
         line["workloads"] = {}
@@ -778,7 +828,7 @@ def main():
     # ---- GPU rate at the chain age of the CPU sample (10 tune asteps of burn-in instead of 100: the CPU leg
     #      cannot afford 100) so that the ratio compares like with like
     matched = None
-    if rank == 0 and world == 1 and solo and not args.no_cpu_baseline and default_cfg and wname == "cfg2":
+    if args.full and rank == 0 and world == 1 and solo and not args.no_cpu_baseline and default_cfg and wname == "cfg2":
         _, stm = make_chain(wname, wkw, seed, be)
         sm = stm.sampler
         run_all([sm], True, CPU_BURN_CFG2)
@@ -791,7 +841,7 @@ def main():
     gpu_done_s = time.perf_counter() - t_start
 
     # ---- CPU baselines, after every GPU leg
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
         cpu = cpu_baseline(wname, wkw, seed, args.cpu_budget, response=args.response)
         line["cpu_baseline"] = cpu
         line["speedup_vs_cpu_baseline"] = line["value"] / cpu["value"]

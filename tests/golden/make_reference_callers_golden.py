@@ -25,6 +25,8 @@ from _oracle import oracle_backend  # noqa: E402
 
 
 def main():
+    if not T.HAVE_REF:
+        raise SystemExit("set PYMC_BART_SRC to a pymc-bart source package (the directory holding utils.py, bart.py)")
     oracle = oracle_backend()
     glue = T.reference_glue(T.bound_to(oracle))
     sys.modules.update(glue["_modules"])

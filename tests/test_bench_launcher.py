@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -20,7 +22,7 @@ def _run(*args, timeout=240):
 
 
 def test_dry_run_two_ranks_over_gloo():
-    r = _run("--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1", "--burnin", "2", "--repeats", "3")
+    r = _run("--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1", "--burnin", "2", "--repeats", "3", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # rank 0 prints ONE line
@@ -43,7 +45,7 @@ def test_dry_run_eight_ranks_over_gloo():
     import time
 
     t0 = time.perf_counter()
-    r = _run("--gpus", "8", "--dry-run", "--steps", "4", "--warmup", "1", "--burnin", "2", "--repeats", "3")
+    r = _run("--gpus", "8", "--dry-run", "--steps", "4", "--warmup", "1", "--burnin", "2", "--repeats", "3", "--full")
     took = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -62,7 +64,7 @@ def test_dry_run_eight_ranks_cfg5_over_gloo():
     """BASELINE.json configs[4] is quoted on 8 GPUs: `bench.py --workload cfg5 --gpus 8` through the launcher, the
     8-way collectives and the end-of-run gather before the driver's node runs it (round-5 VERDICT, next #2)."""
     r = _run("--gpus", "8", "--workload", "cfg5", "--dry-run", "--steps", "3", "--warmup", "1", "--burnin", "2",
-             "--repeats", "2", "--gather-draws", "16")
+             "--repeats", "2", "--gather-draws", "16", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -108,3 +110,71 @@ def test_counter_files_of_other_kernel_sources_are_flagged_stale(tmp_path, monke
         d, src, stale = bench.load_pmc(w)
         if src and src.startswith(f"profiles/{bench.ROUND}_"):
             assert stale is False, (w, src)
+
+
+def test_plain_dry_run_is_the_headline_only():
+    """Without --full the line is the headline: ONE block of exactly --steps asteps, no end-of-run gather."""
+    r = _run("--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1", "--burnin", "2")
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["repeats"] == 1 and d["ms_per_step"] > 0 and d["value"] is None
+    assert "gather_ms" not in d and "resident_path" not in d and list(d)[-1] == "summary"
+
+
+def test_dump_outputs_writes_what_the_astep_returned(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files of sum_trees, the variable-inclusion counts and the step's trees; over the
+    size limit sum_trees becomes a fixed seeded sample with its indices beside it."""
+    import importlib.util
+    import types
+
+    import numpy as np
+
+    from pymc_bart_amd.trees import _HISTORY_FIELDS
+    from pymc_bart_amd.utils import _encode_vi
+
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    trees = types.SimpleNamespace(**{f: rng.integers(0, 9, 12).astype(np.int32) for f in _HISTORY_FIELDS})
+    step = types.SimpleNamespace(num_variates=5, history=(None, [trees]))
+    mu = rng.normal(size=1000)
+    res = (mu, [{"variable_inclusion": _encode_vi([3, 0, 7, 1, 2]), "tune": False}])
+    bench.dump_outputs(str(tmp_path / "a"), res, step)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"sum_trees", "variable_inclusion"} | {f"trees_{f}" for f in _HISTORY_FIELDS}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["sum_trees"], mu) and got["variable_inclusion"].tolist() == [3, 0, 7, 1, 2]
+    assert np.array_equal(got["trees_var"], trees.var)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), res, step)
+    total = sum(p.stat().st_size for p in (tmp_path / "b").glob("*.npy"))
+    idx, sub = np.load(tmp_path / "b" / "sum_trees_index.npy"), np.load(tmp_path / "b" / "sum_trees.npy")
+    assert total <= 4096 and np.array_equal(sub, mu[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "sum_trees_index.npy"))  # the same sample every run
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run on the GPU: --steps timed asteps in one block, the headline fields only, and --dump-outputs
+    identical between two runs with the same arguments."""
+    import numpy as np
+
+    args = ["--steps", "3", "--warmup", "1", "--burnin", "4"]
+    lines = []
+    for d in ("a", "b"):
+        r = _run(*args, "--dump-outputs", str(tmp_path / d), timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["repeats"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "particle-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert not {"roofline", "resident_path", "tune1", "cpu_baseline", "workloads"} & set(d)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    assert set(a) == set(b) and a["sum_trees.npy"].shape == (100_000,)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k

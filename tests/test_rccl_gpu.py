@@ -32,7 +32,7 @@ def _launch(script_args, timeout=600):
 
 def test_bench_rank_under_torchrun_initialises_rccl_and_runs_its_collectives():
     r = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--burnin", "2",
-                 "--repeats", "2", "--no-cpu-baseline", "--no-extras"])
+                 "--repeats", "2", "--no-cpu-baseline", "--no-extras", "--full"])
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # cfg5: likelihood grid 768 (3 workgroups per CU, the old geometry) against the occupancy-derived grid
-mkdir -p gpurun_out/r3v
+O=${1:-build/cfg5_llgrid}; mkdir -p $O
 show() { python - "$1" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -10,7 +10,7 @@ PY
 for rep in 1 2 3; do
   for g in default 768 1280; do
     if [ $g = default ]; then unset PGB_LL_GRID; else export PGB_LL_GRID=$g; fi
-    timeout 300 python bench.py --workload cfg5 --steps 10 --warmup 2 --repeats 8 --no-cpu-baseline --no-multichain --no-extras > gpurun_out/r3v/c5_${g}_$rep.json 2>gpurun_out/r3v/c5_${g}_$rep.err
-    show gpurun_out/r3v/c5_${g}_$rep.json
+    timeout 300 python bench.py --workload cfg5 --steps 10 --warmup 2 --repeats 8 --no-cpu-baseline --no-multichain --no-extras --full > $O/c5_${g}_$rep.json 2>$O/c5_${g}_$rep.err
+    show $O/c5_${g}_$rep.json
   done
 done

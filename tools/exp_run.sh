@@ -3,7 +3,7 @@
 # usage: tools/exp_run.sh TAG "variant1 variant2 ..." ["trace_lib1 trace_lib2 ..."] [extra bench args]
 TAG=$1; VARS=$2; TRACES=$3; shift 3
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O; C=$R/pymc_bart_amd/csrc; V=$R/build/variants
-Q="--steps 20 --warmup 5 --repeats 5 --no-extras --no-cpu-baseline --no-multichain $@"
+Q="--steps 20 --warmup 5 --repeats 5 --no-extras --no-cpu-baseline --no-multichain --full $@"
 for v in $VARS; do
   L=$V/libpgbart_hip_$v.so; [ $v = default ] && L=$C/libpgbart_hip.so
   PGBART_HIP_LIB=$L timeout 300 python bench.py $Q > $O/bench_$v.json 2> $O/bench_$v.err

@@ -6,12 +6,12 @@ if [ "$2" != "quick" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
   tail -3 $O/pytest_gpu.log
 fi
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench rc=$?"
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$TAG
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-multichain --no-extras > $O/under_rocprof_cfg2.json 2> /tmp/prof_$TAG.err
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-multichain --no-extras --full > $O/under_rocprof_cfg2.json 2> /tmp/prof_$TAG.err
 DB=$(find /tmp/prof_$TAG -name "*.db" | head -1)
-echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-multichain --no-extras" > $O/kernel_stats_cfg2.txt
+echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-multichain --no-extras --full" > $O/kernel_stats_cfg2.txt
 python3 $R/tools/rocpd_summary.py $DB --gaps >> $O/kernel_stats_cfg2.txt 2>&1
 head -6 $O/kernel_stats_cfg2.txt
 python3 - <<PY

@@ -16,7 +16,7 @@ BUDGET = os.path.join(ROOT, "profiles", "latency_budget.json")
 
 def measure():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--repeats", "20",
-           "--no-extras", "--no-cpu-baseline", "--no-multichain", "--no-workloads"]
+           "--no-extras", "--no-cpu-baseline", "--no-multichain", "--no-workloads", "--full"]
     runs = []
     for _ in range(3):
         out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600).stdout

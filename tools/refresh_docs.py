@@ -31,7 +31,7 @@ def us(leg):
 
 
 rf, r4, r5, rr4, rr5 = d["roofline"], w4["roofline"], w5["roofline"], w4["roofline_rows"], w5["roofline_rows"]
-design = f"""`python tools/show_bench.py --table profiles/{RND}_bench.json` (the line `python bench.py` printed on the last source state
+design = f"""`python tools/show_bench.py --table profiles/{RND}_bench.json` (the line `python bench.py --full` printed on the last source state
 of the round, `tools/final_profiles.sh`; BASELINE.md §3's table, every row from that ONE line):
 
 {tab}
@@ -59,7 +59,7 @@ two-kernel slot, flags instead of kernel boundaries, graphs, grid barriers).  CP
 on the box ({d['cpu_baseline']['host']['cpu_model']}, {d['cpu_baseline']['host']['nproc']} cores visible), a restatement — the reference's sampler cannot run
 here (§0)."""
 readme = f"""Measured on one MI355X (round {int(RND[1:])}, steady state after 10 tuning sweeps, one chain per GPU; every row below comes
-from the ONE line `python bench.py` prints — `profiles/{RND}_bench.json` — and the table itself is the output of
+from the ONE line `python bench.py --full` prints — `profiles/{RND}_bench.json` — and the table itself is the output of
 `python tools/show_bench.py --table profiles/{RND}_bench.json`, the form of BASELINE.md's results table):
 
 {tab}"""

@@ -3,7 +3,7 @@
 
   python tools/show_bench.py FILE...            one line per file: value, ms / astep, kernels, roofline
   python tools/show_bench.py --table FILE       BASELINE.md's results table (section 3), filled from the ONE line
-                                                `python bench.py` prints (BENCH_rNN.json's "parsed" object works too)
+                                                `python bench.py --full` prints (BENCH_rNN.json's "parsed" object works too)
 README.md's table is the output of --table on the committed line (profiles/rNN_bench.json)."""
 import json
 import sys

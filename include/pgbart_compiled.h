@@ -1,0 +1,113 @@
+/*
+ * pgbart_compiled.h -- the "compiled" likelihood family: a per-row log-density written by the user as a
+ * short C function body, compiled at run time into a k_loglik instance for gfx950 (a code object the HIP
+ * library loads) and, for the CPU backends, into a host function with the pgb_loglik_fn signature.
+ *
+ * Kept apart from pgbart.h on purpose: pgbart.h is the ABI every backend (the CPU oracle included) exports in
+ * full; the entry points below exist in the HIP library only.  A CPU backend runs the same body as family
+ * PGB_FAMILY_CALLBACK with the host build installed as its callback (pymc_bart_amd/compiled.py).
+ *
+ * The body is the inside of
+ *     double f(double y, double mu, double aux, const double <param 0>, ..., const double <param n-1>)
+ * (at most PGB_COMPILED_MAX_PARAMS params).  Its vocabulary -- the only functions it may call -- is defined
+ * ONCE here for both compiles (section "vocabulary"): the table functions of pgbart_spec.h (bit-identical on
+ * the host and the device) and explicit comparisons, no libm.  Both compiles run with -ffp-contract=off.
+ * The result goes through the contract's clamp ([-2047, 2047], NaN -> -2047) and the fixed-point sums of the
+ * callback family: on a given backend the compiled family and the callback family are the same sampler.
+ */
+#ifndef PGBART_COMPILED_H
+#define PGBART_COMPILED_H
+
+#include <stdint.h>
+
+#define PGB_FAMILY_COMPILED 11    /* y ~ a per-row log-density compiled at run time (this header) */
+#define PGB_COMPILED_MAX_PARAMS 8
+#define PGB_COMPILED_MAGIC 0x43424750 /* "PGBC" */
+#define PGB_COMPILED_KERNEL "k_loglik_compiled"
+#define PGB_COMPILED_LAYOUT "pgb_compiled_layout_record"
+
+/* The layout record every compiled code object carries (a __device__ global named PGB_COMPILED_LAYOUT): the
+ * library compares it with its own values before the first launch and refuses a code object built for the
+ * other particle build or from other kernel headers. */
+typedef struct {
+  int32_t magic;          /* PGB_COMPILED_MAGIC */
+  int32_t max_particles;  /* PGB_MAX_PARTICLES */
+  int32_t n_params;       /* params the body was compiled for */
+  int32_t pad;
+  int64_t sizeof_dev, sizeof_job, sizeof_cmd, sizeof_ctrl, sizeof_acc;
+  uint64_t headers_hash;  /* PGB_HEADERS_HASH: a hash of the kernel headers (pymc_bart_amd/compiled.py) */
+} pgb_compiled_layout;
+
+/* The params of one launch, by value (they arrive in SGPRs with the kernel arguments). */
+typedef struct {
+  double v[PGB_COMPILED_MAX_PARAMS];
+} pgb_compiled_params;
+
+#if !defined(PGB_COMPILED_NO_ENTRY_POINTS)
+#include "pgbart.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* Load a compiled code object (hipModuleLoadData) for a sampler created with family PGB_FAMILY_COMPILED and
+ * check its layout record.  PGB_E_INVALID for another family, bytes that are not a gfx950 code object, a code
+ * object without the kernel or the record, or a record that does not match this library; the handle stays usable
+ * (a refused image is never launched).  A new code object replaces the old one; pgb_destroy unloads it.
+ * n_params: the params the body declares (pgb_set_likelihood then takes exactly that many). */
+int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64_t bytes, int32_t n_params);
+/* Optional per-row column `aux` (n doubles, device memory) the body reads as `aux`; NULL clears it (aux = 0.0).
+ * Non-finite values are refused (PGB_E_INVALID) and the column is cleared. */
+int pgb_set_loglik_aux(pgb_handle* h, const double* aux_dev);
+#ifdef __cplusplus
+}
+#endif
+#endif
+
+#endif /* PGBART_COMPILED_H */
+
+/* ------------------------------------------------------------------ vocabulary
+ * (outside the include guard: a unit that compiles a body includes this header again around it)
+ * The unit defines, right in front of the body:
+ *   PGB_COMPILED_VOCABULARY                    then includes this header: the vocabulary is on
+ *   PGB_CL_EXPT / PGB_CL_LOGT / PGB_CL_LPHI   the tables (host: pgb_tab_*(); device: the kernel's copies)
+ * and behind it PGB_COMPILED_VOCABULARY_END (and includes this header again): the names are released.
+ * The functions are macros so that the same text serves C (host) and HIP (device):
+ *   exp, log         pgb_exp_t, pgb_log_t             (pgbart_spec.h: table-driven, the same bits on both sides)
+ *   log_ndtr         pgb_lphi_t                       (log Phi, the probit family's function)
+ *   softplus         pgb_softplus_t                   (log(1 + e^x))
+ *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour) */
+#if defined(PGB_COMPILED_VOCABULARY) && !defined(PGB_COMPILED_VOCABULARY_ON)
+#define PGB_COMPILED_VOCABULARY_ON
+#ifndef PGB_COMPILED_VOCABULARY_FNS
+#define PGB_COMPILED_VOCABULARY_FNS
+#include "pgbart_spec.h"
+/* fabs(-0.0) = +0.0, a NaN stays a NaN; fmin / fmax return the SECOND argument when the comparison fails (a NaN
+ * in either) */
+PGB_HD double pgb_cl_fabs(double x) { return x < 0.0 ? -x : x + 0.0; }
+PGB_HD double pgb_cl_fmin(double a, double b) { return a < b ? a : b; }
+PGB_HD double pgb_cl_fmax(double a, double b) { return a > b ? a : b; }
+/* pgb_softplus_t on the two tables (the same operations) */
+PGB_HD double pgb_cl_softplus(double t, const double* expt, const double* logt) {
+  if (t > 36.0) return t;
+  return pgb_log_t(1.0 + pgb_exp_t(t, expt), logt);
+}
+#endif
+#define exp(x) pgb_exp_t((double)(x), PGB_CL_EXPT)
+#define log(x) pgb_log_t((double)(x), PGB_CL_LOGT)
+#define log_ndtr(x) pgb_lphi_t((double)(x), PGB_CL_LPHI)
+#define softplus(x) pgb_cl_softplus((double)(x), PGB_CL_EXPT, PGB_CL_LOGT)
+#define fabs(x) pgb_cl_fabs((double)(x))
+#define fmin(a, b) pgb_cl_fmin((double)(a), (double)(b))
+#define fmax(a, b) pgb_cl_fmax((double)(a), (double)(b))
+#endif
+#if defined(PGB_COMPILED_VOCABULARY_END) && defined(PGB_COMPILED_VOCABULARY_ON)
+#undef PGB_COMPILED_VOCABULARY_ON
+#undef PGB_COMPILED_VOCABULARY
+#undef PGB_COMPILED_VOCABULARY_END
+#undef exp
+#undef log
+#undef log_ndtr
+#undef softplus
+#undef fabs
+#undef fmin
+#undef fmax
+#endif

@@ -9,6 +9,7 @@ from . import _abi
 from .pgbart import (PGBART, AsymmetricLaplaceLikelihood, BARTOp, BernoulliLikelihood, CallbackLikelihood, GammaLikelihood, CategoricalLikelihood, NegativeBinomialLikelihood,
                      NormalLikelihood, NormalMeanScaleLikelihood, PoissonLikelihood, StudentTLikelihood)
 from .sampler import PyBartSettings, PySampler
+from .compiled import CompiledLikelihood, CompileError, compile_loglik
 from .trees import PosteriorSampler, TreeArrays
 from .importance import compute_variable_importance, get_variable_inclusion, vi_to_kulprit
 from .partial import individual_conditional_expectation, partial_dependence
@@ -32,7 +33,7 @@ _register_step_method()
 
 __version__ = "0.1.0"
 __all__ = [
-    "PGBART", "BARTOp", "CallbackLikelihood", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
+    "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
     "partial_dependence", "individual_conditional_expectation", "_abi",
 ]

@@ -53,6 +53,7 @@ FAMILIES = {
     "student_t": 8,
     "gamma_log": 9,
     "callback": 10,
+    "compiled": 11,  # include/pgbart_compiled.h: HIP library only (a CPU backend runs the host build as "callback")
 }
 
 #: every symbol ``include/pgbart.h`` declares (checked by tests/test_abi.py)
@@ -217,6 +218,16 @@ class PGBLibrary:
                 fn.restype = C.c_int
         lib.pgb_max_particles.argtypes = []
         lib.pgb_abi_version.argtypes = []
+
+    def compiled_entry_points(self):
+        """``pgb_set_loglik_code`` / ``pgb_set_loglik_aux`` (include/pgbart_compiled.h: not part of the ABI every
+        backend exports, hence not in SYMBOLS)."""
+        lib = self.lib
+        lib.pgb_set_loglik_code.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+        lib.pgb_set_loglik_code.restype = C.c_int
+        lib.pgb_set_loglik_aux.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pgb_set_loglik_aux.restype = C.c_int
+        return lib.pgb_set_loglik_code, lib.pgb_set_loglik_aux
 
     @property
     def backend_name(self) -> str:

@@ -20,12 +20,13 @@ from .utils import _decode_vi
 
 def sample_chain(op: BARTOp, tune: int, draws: int, num_particles: int = 10, random_seed: int = 0,
                  chain: int = 0, batch=(0.1, 0.1), sigma: float | None = None,
-                 sigma_prior=(1.0, 1.0), backend=None, keep_draws: bool = True) -> dict:
+                 sigma_prior=(1.0, 1.0), backend=None, keep_draws: bool = True, likelihood=None) -> dict:
     """Run one chain.  ``sigma=None``: sigma^2 ~ InvGamma(a0, b0) is Gibbs-updated from the
     residuals after every step (conjugate stand-in for the HalfNormal+NUTS of the reference
-    tests); otherwise sigma is held fixed."""
+    tests); otherwise sigma is held fixed.  ``likelihood``: another likelihood object than the default
+    ``NormalLikelihood("sigma")`` (e.g. a :class:`~pymc_bart_amd.CompiledLikelihood`; no sigma update then)."""
     rng = np.random.default_rng(np.random.SeedSequence([int(random_seed), int(chain), 77]))
-    lik = NormalLikelihood("sigma")
+    lik = NormalLikelihood("sigma") if likelihood is None else likelihood
     step = PGBART([op], num_particles=num_particles, batch=batch, likelihood=lik,
                   random_seed=random_seed, chain=chain, backend=backend)
     Y = np.asarray(op.Y, np.float64)
@@ -39,7 +40,7 @@ def sample_chain(op: BARTOp, tune: int, draws: int, num_particles: int = 10, ran
             step.stop_tuning()
         point = {"sigma": cur_sigma}
         mu, stats = step.astep(None, point)
-        if sigma is None:
+        if sigma is None and lik.family == "normal":
             res = Y - mu
             a0, b0 = sigma_prior
             cur_sigma = float(np.sqrt((b0 + 0.5 * float(res @ res)) / rng.gamma(a0 + 0.5 * n)))

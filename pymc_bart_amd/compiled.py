@@ -1,0 +1,437 @@
+"""Custom per-row likelihoods compiled at run time: family ``"compiled"`` (``include/pgbart_compiled.h``).
+
+The user writes the log-density of ONE observation as a short C function body; :func:`compile_loglik` turns it
+into
+
+* a gfx950 code object: ``csrc/k_loglik_compiled.hip`` -- the library's one-output log-likelihood pass with the body
+  at every evaluation site -- compiled with the library's device flags plus ``--genco``.  The HIP library loads it
+  (``pgb_set_loglik_code``) and the chain stays device-resident: no host round trip per SMC round;
+* a host function with the ``pgb_loglik_fn`` signature (gcc, the oracle's flags), which any CPU backend runs as
+  family ``"callback"`` -- natively, no Python in the per-row loop.
+
+Both sides evaluate the body with the same vocabulary (table-driven ``exp`` / ``log`` / ``log_ndtr`` /
+``softplus`` of ``include/pgbart_spec.h`` and explicit comparisons), so that a CPU backend checks the GPU chain bit
+for bit.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
+everything that goes into them.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import hashlib
+import json
+import os
+import re
+import subprocess
+import tempfile
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(ROOT, "include")
+TU = os.path.join(CSRC, "k_loglik_compiled.hip")
+LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+
+#: the library's device flags (``__graft_entry__.HIPCC_FLAGS`` without ``-fPIC`` / ``-shared``; a test holds them equal)
+DEVICE_FLAGS = [
+    "--offload-arch=gfx950", "-O3", "-std=c++17",
+    "-ffp-contract=off",
+    f"-I{INCLUDE}",
+    "-mllvm", "-amdgpu-kernarg-preload-count=16",
+]
+#: what turns the unit into one raw gfx950 code object (an ELF the runtime loads with hipModuleLoadData)
+GENCO_FLAGS = ["--genco", "--no-gpu-bundle-output"]
+#: the host build: the oracle's flags
+HOST_FLAGS = ["-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared"]
+
+MAX_PARAMS = 8
+#: what a body may call (include/pgbart_compiled.h, section "vocabulary")
+VOCABULARY = {
+    "exp": "exp(x): pgb_exp_t, the spec's table-driven exponential",
+    "log": "log(x): pgb_log_t (x <= 0 -> -1e300, NaN stays NaN)",
+    "log_ndtr": "log_ndtr(x): log Phi(x), pgb_lphi_t",
+    "softplus": "softplus(x): log(1 + e^x), pgb_softplus_t",
+    "fabs": "fabs(x): x < 0 ? -x : x + 0.0",
+    "fmin": "fmin(a, b): a < b ? a : b",
+    "fmax": "fmax(a, b): a > b ? a : b",
+}
+_EXPLOG = ("exp", "log", "softplus")
+_C_KEYWORDS = {
+    "auto", "break", "case", "char", "const", "continue", "default", "do", "double", "else", "enum", "extern",
+    "float", "for", "goto", "if", "inline", "int", "long", "register", "restrict", "return", "short", "signed",
+    "sizeof", "static", "struct", "switch", "typedef", "union", "unsigned", "void", "volatile", "while", "asm",
+    "_Bool", "_Thread_local", "bool", "true", "false", "class", "template", "this", "new", "delete", "namespace",
+    "using", "operator", "typename", "virtual", "constexpr", "thread_local", "static_assert", "alignas", "alignof",
+}
+#: keywords a body may not use: storage that would outlive the call, declarations outside the function
+_REFUSED_KEYWORDS = {"static", "extern", "register", "volatile", "_Thread_local", "thread_local", "typedef", "goto",
+                     "struct", "union", "enum", "class", "template", "namespace", "using", "operator", "new", "delete",
+                     "asm", "inline"}
+_CALLABLE_KEYWORDS = {"if", "while", "for", "switch", "return", "sizeof", "int", "double", "float", "long", "unsigned",
+                      "signed", "char", "short", "const"}
+_IDENT = re.compile(r"[A-Za-z_][A-Za-z0-9_]*")
+
+
+class CompileError(RuntimeError):
+    """A body the compilers refuse (or one that calls a function outside the vocabulary)."""
+
+
+def vocabulary_text() -> str:
+    return "; ".join(VOCABULARY.values()) + "; plus + - * /, comparisons, ?:, if, local double / int variables"
+
+
+# ---------------------------------------------------------------------------------------------------- validation
+def _strip_comments(body: str) -> str:
+    body = re.sub(r"/\*.*?\*/", lambda m: " " * len(m.group(0)), body, flags=re.S)
+    return re.sub(r"//[^\n]*", "", body)
+
+
+def validate(body: str, param_names) -> tuple[str, ...]:
+    """Refuse, before any compiler runs, what the body may not contain.  Returns the param names as a tuple."""
+    if not isinstance(body, str) or not body.strip():
+        raise ValueError("the body must be a non-empty string of C statements")
+    names = tuple(param_names)
+    if len(names) > MAX_PARAMS:
+        raise ValueError(f"at most {MAX_PARAMS} params, {len(names)} given")
+    seen = set()
+    for nm in names:
+        if not isinstance(nm, str) or not re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", nm):
+            raise ValueError(f"param name {nm!r} is not a C identifier")
+        if nm in ("y", "mu", "aux"):
+            raise ValueError(f"param name {nm!r} clashes with the body's arguments y, mu, aux")
+        if nm in VOCABULARY:
+            raise ValueError(f"param name {nm!r} clashes with the vocabulary ({', '.join(VOCABULARY)})")
+        if nm in _C_KEYWORDS:
+            raise ValueError(f"param name {nm!r} is a C keyword")
+        if nm.startswith("__") or nm.lower().startswith("pgb_"):
+            raise ValueError(f"param name {nm!r}: names starting with '__' or 'pgb_' are reserved")
+        if nm in seen:
+            raise ValueError(f"duplicate param name {nm!r}")
+        seen.add(nm)
+    for lineno, line in enumerate(body.splitlines(), 1):
+        if line.lstrip().startswith("#") or line.lstrip().startswith("%:"):
+            raise ValueError(f"line {lineno}: preprocessor lines are not allowed in a likelihood body: {line.strip()!r}")
+    # (on the raw text: no line splice can move code into or out of a comment)
+    for bad, what in (("#", "'#' (preprocessor)"), ("%:", "'%:' (preprocessor digraph)"), ("??", "'??' (trigraph)"),
+                      ("\\", "a backslash")):
+        if bad in body:
+            raise ValueError(f"the body contains {what}: not allowed in a likelihood body")
+    code = _strip_comments(body)
+    for bad, what in (('"', "a string literal"), ("'", "a character literal")):
+        if bad in code:
+            raise ValueError(f"the body contains {what}: not allowed in a likelihood body")
+    for m in _IDENT.finditer(code):
+        tok = m.group(0)
+        if tok in ("asm", "__asm__", "__asm") or tok.startswith("__asm"):
+            raise ValueError(f"inline assembly ({tok!r}) is not allowed in a likelihood body")
+        if tok.startswith("__builtin"):
+            raise ValueError(f"compiler builtins ({tok!r}) are not allowed in a likelihood body; the vocabulary: "
+                             + ", ".join(VOCABULARY))
+        if tok.startswith("__"):
+            raise ValueError(f"identifiers starting with '__' ({tok!r}) are reserved")
+        if tok.lower().startswith("pgb_"):
+            raise ValueError(f"identifiers starting with 'pgb_' ({tok!r}) are reserved for the prelude")
+        if tok in _REFUSED_KEYWORDS:
+            raise ValueError(f"{tok!r} is not allowed in a likelihood body (local double / int variables only)")
+    depth = 0
+    for ch in code:  # the body stays inside its function
+        depth += ch == "{"
+        depth -= ch == "}"
+        if depth < 0:
+            raise ValueError("unbalanced '}' in the body")
+    if depth != 0:
+        raise ValueError("unbalanced '{' in the body")
+    for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_]*)\s*\(", code):
+        fn = m.group(1)
+        if fn in VOCABULARY or fn in _CALLABLE_KEYWORDS:
+            continue
+        lineno = code.count("\n", 0, m.start()) + 1
+        raise CompileError(f"line {lineno}: {fn!r} is not in the likelihood vocabulary:\n    "
+                           f"{body.splitlines()[lineno - 1].strip()}\nthe vocabulary: {vocabulary_text()}")
+    return names
+
+
+def uses_tables(body: str) -> bool:
+    """Whether the body calls exp / log / softplus (the kernel then stages their tables in LDS)."""
+    code = _strip_comments(body)
+    return any(re.search(rf"\b{f}\s*\(", code) for f in _EXPLOG)
+
+
+# ---------------------------------------------------------------------------------------------------- keys, cache
+def _header_files() -> list[str]:
+    files = [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
+    files += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
+    return files + [TU]
+
+
+def headers_hash() -> int:
+    """64-bit hash of every header the code object and the library are built from (and of the unit itself): the
+    library is compiled with it (``-DPGB_HEADERS_HASH``) and refuses a code object that carries another."""
+    h = hashlib.sha256()
+    for f in _header_files():
+        h.update(os.path.basename(f).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    v = int.from_bytes(h.digest()[:8], "little")
+    return v or 1
+
+
+def hipcc_path() -> str:
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+_HIPCC_VERSION: dict = {}
+
+
+def _hipcc_version(hipcc: str) -> str:
+    if hipcc not in _HIPCC_VERSION:
+        _HIPCC_VERSION[hipcc] = subprocess.run([hipcc, "--version"], capture_output=True, text=True).stdout
+    return _HIPCC_VERSION[hipcc]
+
+
+def cache_dir() -> str:
+    return os.environ.get("PGB_JIT_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "pymc_bart_amd", "jit")
+
+
+def cache_key(body: str, param_names, max_particles: int = 64) -> str:
+    h = hashlib.sha256()
+    h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
+                         "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
+                         "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
+                        sort_keys=True).encode())
+    return h.hexdigest()[:32]
+
+
+def _write_atomic(path: str, data: bytes) -> None:
+    d = os.path.dirname(path)
+    fd, tmp = tempfile.mkstemp(dir=d, prefix=".tmp_", suffix=os.path.basename(path))
+    try:
+        with os.fdopen(fd, "wb") as fh:
+            fh.write(data)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+
+
+# ---------------------------------------------------------------------------------------------------- the builds
+def _body_defs(names, max_particles: int, explog: bool) -> str:
+    return "\n".join([
+        f"#define PGB_COMPILED_NPARAMS {len(names)}",
+        f"#define PGB_COMPILED_EXPLOG {1 if explog else 0}",
+        f"#define PGB_HEADERS_HASH {headers_hash()}ull",
+        "#define PGB_COMPILED_PARAMS " + "".join(f", const double {nm}" for nm in names),
+        "#define PGB_COMPILED_ARGS(P) " + "".join(f", (P).v[{i}]" for i in range(len(names))),
+        "",
+    ])
+
+
+def _body_text(body: str) -> str:
+    return '#line 1 "loglik body"\n' + body + "\n"
+
+
+def _host_source(body: str, names) -> str:
+    params = "".join(f", const double {nm}" for nm in names)
+    args = "".join(f", c->params[{i}]" for i in range(len(names)))
+    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood body */
+#include <stdint.h>
+#include <stddef.h>
+#define PGB_COMPILED_NO_ENTRY_POINTS
+#include "pgbart_spec.h"
+#include "pgbart_compiled.h"
+#define PGB_CL_EXPT pgb_tab_exp()
+#define PGB_CL_LOGT pgb_tab_log()
+#define PGB_CL_LPHI pgb_tab_lphi()
+#define PGB_COMPILED_VOCABULARY
+#include "pgbart_compiled.h"
+static double pgb_compiled_user(double y, double mu, double aux{params}) {{
+{_body_text(body)}}}
+#define PGB_COMPILED_VOCABULARY_END
+#include "pgbart_compiled.h"
+typedef struct {{
+  const double* aux;
+  double params[PGB_COMPILED_MAX_PARAMS];
+}} pgb_compiled_ctx;
+/* pgb_loglik_fn: the row index selects aux; the library clamps and quantises the values */
+int pgb_compiled_loglik(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out) {{
+  const pgb_compiled_ctx* c = (const pgb_compiled_ctx*)ctx;
+  for (int64_t i = 0; i < n; ++i) out[i] = pgb_compiled_user(y[i], mu[i], c->aux ? c->aux[row[i]] : 0.0{args});
+  return 0;
+}}
+"""
+
+
+def _compile_error(stderr: str, body: str, side: str) -> CompileError:
+    lines = body.splitlines()
+    msgs = []
+    for m in re.finditer(r"loglik body:(\d+):(?:\d+:)?\s*(?:fatal )?error:\s*(.*)", stderr):
+        ln = int(m.group(1))
+        src = lines[ln - 1].strip() if 1 <= ln <= len(lines) else ""
+        msgs.append(f"line {ln}: {m.group(2).strip()}\n    {src}")
+    if not msgs:
+        tail = [ln for ln in stderr.splitlines() if "error" in ln][:5]
+        msgs = tail or [stderr.strip()[-2000:]]
+    return CompileError(f"the likelihood body does not compile ({side}):\n" + "\n".join(msgs[:5])
+                        + f"\nthe vocabulary: {vocabulary_text()}")
+
+
+def kernel_resources(code_object_path: str) -> dict:
+    """VGPR / SGPR / scratch / LDS / spills / workgroups per CU of ``k_loglik_compiled``, from the code object's
+    metadata note -- the way tools/occupancy_guard.py reads the library's."""
+    import yaml
+
+    notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", code_object_path], text=True)
+    start = notes.index("---\n") + 4
+    end = notes.index("\n...", start) if "\n..." in notes[start:] else len(notes)
+    meta = yaml.safe_load(notes[start:end])
+    for k in meta["amdhsa.kernels"]:
+        if k[".name"] == "k_loglik_compiled":
+            vg, ag = int(k[".vgpr_count"]), int(k.get(".agpr_count", 0))
+            lds = int(k[".group_segment_fixed_size"])
+            unified = ((vg + 3) // 4) * 4 + ag
+            alloc = -(-unified // 8) * 8
+            waves = max(1, min(8, 512 // max(alloc, 8)))
+            wgs = min(waves * 4 // 4, (160 * 1024) // lds if lds else 1 << 30, 8)
+            return {"vgpr": vg, "agpr": ag, "sgpr": int(k[".sgpr_count"]), "lds_bytes": lds,
+                    "scratch_bytes": int(k[".private_segment_fixed_size"]),
+                    "vgpr_spills": int(k.get(".vgpr_spill_count", 0)), "sgpr_spills": int(k.get(".sgpr_spill_count", 0)),
+                    "wgs_per_cu": wgs}
+    raise CompileError("the code object has no kernel k_loglik_compiled")
+
+
+class CompiledLoglik:
+    """One build of a body: the code object (``code``), the host library (``host_lib``), the kernel's resource
+    usage (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit."""
+
+    def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached):
+        self.key, self.body, self.param_names, self.max_particles = key, body, tuple(param_names), int(max_particles)
+        self.code, self.host_lib, self.resources = code, host_lib, resources
+        self.compile_seconds, self.cached = compile_seconds, cached
+        self._host = None
+
+    @property
+    def n_params(self) -> int:
+        return len(self.param_names)
+
+    def host_function(self):
+        """The host build's ``pgb_compiled_loglik`` as a ctypes function (``pgb_loglik_fn``)."""
+        from . import _abi
+
+        if self._host is None:
+            self._host = _abi.LOGLIK_FN(("pgb_compiled_loglik", C.CDLL(self.host_lib)))
+        return self._host
+
+
+class CompiledContext(C.Structure):
+    """``ctx`` of the host build: the aux column (or NULL) and the params."""
+
+    _fields_ = [("aux", C.c_void_p), ("params", C.c_double * MAX_PARAMS)]
+
+
+def compile_loglik(body: str, param_names=(), max_particles: int = 64) -> CompiledLoglik:
+    """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
+    (64 or 128) -- or take it from the cache."""
+    names = validate(body, param_names)
+    mp = 128 if int(max_particles) > 64 else 64
+    key = cache_key(body, names, mp)
+    root = cache_dir()
+    os.makedirs(root, exist_ok=True)
+    co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
+    if os.path.exists(meta_path) and os.path.exists(co_path) and os.path.exists(so_path):
+        with open(meta_path) as fh:
+            meta = json.load(fh)
+        with open(co_path, "rb") as fh:
+            code = fh.read()
+        return CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True)
+    t0 = time.perf_counter()
+    with tempfile.TemporaryDirectory(prefix="pgb_jit_") as tmp:
+        # host first: quick, and the compiler's messages about the body are the same on either side
+        src = os.path.join(tmp, "host.c")
+        with open(src, "w") as fh:
+            fh.write(_host_source(body, names))
+        so_tmp = os.path.join(tmp, "host.so")
+        r = subprocess.run(["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", src,
+                            "-o", so_tmp, "-lm"], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise _compile_error(r.stderr, body, "host")
+        with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
+            fh.write(_body_defs(names, mp, uses_tables(body)))
+        with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
+            fh.write(_body_text(body))
+        co_tmp = os.path.join(tmp, "k.co")
+        cmd = [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, f"-DPGB_MAX_PARTICLES={mp}", f"-I{CSRC}", f"-I{tmp}", "-w",
+               TU, "-o", co_tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise _compile_error(r.stderr, body, "device")
+        resources = kernel_resources(co_tmp)
+        seconds = time.perf_counter() - t0
+        with open(co_tmp, "rb") as fh:
+            code = fh.read()
+        with open(so_tmp, "rb") as fh:
+            host = fh.read()
+    _write_atomic(co_path, code)
+    _write_atomic(so_path, host)
+    meta = {"body": body, "params": list(names), "max_particles": mp, "resources": resources,
+            "compile_seconds": seconds}
+    _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
+    return CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False)
+
+
+class CompiledLikelihood:
+    """A per-row log-likelihood written as a C function body, compiled for the GPU at run time.
+
+    ``body`` is the inside of ``double f(double y, double mu, double aux, const double <param>...)``:
+
+    * ``y``   the observed value of the row, ``mu`` its linear predictor (sum of trees plus offset),
+    * ``aux`` the row's entry of the optional per-row column ``aux`` (0.0 without one),
+    * one ``const double`` per entry of ``params`` (at most 8), in the order given.
+
+    ``params`` maps each name to a number or to the name of a point variable (read like the built-in families'
+    parameters: a number, a shared variable, a callable, or a key of the point).
+
+    The vocabulary: IEEE ``+ - * /``, comparisons, ``?:``, ``if``, local ``double`` and ``int`` variables, and
+    ``exp``, ``log`` (the spec's table functions), ``log_ndtr`` (log Phi), ``softplus`` (log(1 + e^x)), ``fabs``,
+    ``fmin``, ``fmax`` (explicit comparisons).  Nothing from libm (no ``sqrt``, ``pow``): the same body must give the
+    same bits on the GPU and on the CPU.  No preprocessor lines, no ``asm``, no ``__``-names.
+
+    The value is clamped to [-2047, 2047] (NaN -> -2047) and summed in fixed point exactly like family
+    ``"callback"``; on the GPU the evaluation runs inside the sampler's own likelihood kernel.
+
+    >>> CompiledLikelihood("double u = (y - mu) / b;  return -(u * (u < 0.0 ? q - 1.0 : q));",
+    ...                    params={"b": 0.25, "q": "q_var"})            # doctest: +SKIP
+    """
+
+    family = "compiled"
+
+    def __init__(self, body: str, params=None, aux=None):
+        self.body = body
+        self.param_spec = dict(params or {})
+        self.param_names = validate(body, list(self.param_spec))
+        self.aux = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).ravel()
+        if self.aux is not None and not np.all(np.isfinite(self.aux)):
+            raise ValueError("aux must be finite")
+        self._builds = {}
+        self.compiled(64)  # (errors surface here, not at the first step)
+
+    def compiled(self, max_particles: int = 64) -> CompiledLoglik:
+        mp = 128 if int(max_particles) > 64 else 64
+        if mp not in self._builds:
+            self._builds[mp] = compile_loglik(self.body, self.param_names, mp)
+        return self._builds[mp]
+
+    def params(self, point=None):
+        from .pgbart import _from_point
+
+        return [_from_point(v, point) for v in self.param_spec.values()]
+
+    def __getstate__(self):
+        return {"body": self.body, "params": self.param_spec, "aux": self.aux}
+
+    def __setstate__(self, d):
+        self.__init__(d["body"], d["params"], d["aux"])

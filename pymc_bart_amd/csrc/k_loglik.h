@@ -174,6 +174,25 @@ __device__ __forceinline__ long long quant_ll(double ll, double cl) {
   return (long long)(pgb_d2u(mg) - 0x4338000000000000ull);
 }
 
+// The compiled family (PGB_FAMILY_COMPILED, include/pgbart_compiled.h) has no instance in the library: its code
+// object is k_loglik_compiled.hip, which includes this header with PGB_COMPILED_LOGLIK defined and a generated
+// pgb_compiled_eval(y, mu, aux, params, tables) in front of it.  There k_loglik is the __forceinline__ body of the
+// kernel k_loglik_compiled, with two arguments more: the aux column ([n_pad], like y) and the params (by value).
+#ifdef PGB_COMPILED_LOGLIK
+#define PGB_LL_ENTRY(WGS) __device__ __forceinline__
+#define PGB_LL_EXTRA_ARGS , const double* __restrict__ cl_aux, const pgb_compiled_params cl_prm
+#define PGB_CL_AUX(row) cl_aux[row]
+#define PGB_CL_LL(y, mu, aux) pgb_compiled_eval((y), (mu), (aux), cl_prm, &tb)
+#else
+#define PGB_LL_ENTRY(WGS) __global__ __launch_bounds__(BT, WGS)
+#define PGB_LL_EXTRA_ARGS
+#define PGB_CL_AUX(row) 0.0
+#define PGB_CL_LL(y, mu, aux) 0.0
+#endif
+#ifndef PGB_COMPILED_EXPLOG
+#define PGB_COMPILED_EXPLOG 1 /* the compiled body calls exp / log / softplus: stage their tables in LDS */
+#endif
+
 // KT: 1 = single output; 2, 3, 4 = that many outputs, loops unrolled; 0 = any K <= PGB_MAX_OUTPUTS
 // FAM: the likelihood family when known at compile time (single-output kernels: the per-row
 // evaluation then contains one family's code only), -1: read S.family.
@@ -182,9 +201,10 @@ template <int KT, int FAM, bool LIN>
 // (compiled for 3 workgroups per CU, i.e. <= 168 VGPRs: the K = 4 instance sits right at that edge, and one
 //  register more costs it a third of its waves -- 32 -> 40 us per launch at cfg5;
 //  the probit instance -- cfg4's dominant kernel -- for 5: <= 96 VGPRs, where a 97th costs it a fifth)
-__global__ __launch_bounds__(BT, (KT == 1 && FAM == PGB_FAMILY_BERNOULLI_PROBIT && !LIN) ? 5 : (KT >= 2 && !LIN) ? PGB_LLK_WGS : KT == 0 ? 2 : 3)
+PGB_LL_ENTRY((KT == 1 && FAM == PGB_FAMILY_BERNOULLI_PROBIT && !LIN) ? 5 : (KT >= 2 && !LIN) ? PGB_LLK_WGS : KT == 0 ? 2 : 3)
 void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restrict__ cmds, const Ctrl* __restrict__ ctrls,
-              const Job* __restrict__ jobs_all, const Acc* __restrict__ acc_all, const InitAcc* __restrict__ ias) {
+              const Job* __restrict__ jobs_all, const Acc* __restrict__ acc_all, const InitAcc* __restrict__ ias
+              PGB_LL_EXTRA_ARGS) {
   // cmds / ctrls / jobs_all / acc_all / ias repeat S.cmd / S.ctrl / S.jobs / S.acc / S.initacc as kernel arguments
   // (preloaded into SGPRs): the first loads of the launch -- the command word, the control word, the job records and
   // their statistics -- go out together, at once, instead of behind a load of their pointers from the argument block
@@ -238,8 +258,9 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
   // instance (10.4 KB, coefficient-major: lanes reading coefficient k of different rows hit different banks),
   // exp / log (2.3 KB) for every instance whose family uses them
   constexpr bool PROBIT = KT == 1 && FAM == PGB_FAMILY_BERNOULLI_PROBIT;
+  constexpr bool CMPL = KT == 1 && FAM == PGB_FAMILY_COMPILED;  // (plain path, aux column, params in registers)
   constexpr bool EXPLOG = !(KT == 1 && (FAM == PGB_FAMILY_BERNOULLI_PROBIT || FAM == PGB_FAMILY_ASYMLAPLACE ||
-                                        FAM == PGB_FAMILY_CALLBACK));
+                                        FAM == PGB_FAMILY_CALLBACK)) && (!CMPL || PGB_COMPILED_EXPLOG);
   __shared__ __attribute__((aligned(16))) double s_lphi[PROBIT ? PGB_LPHI_SIZE : 2];
   __shared__ __attribute__((aligned(16))) double s_expt[EXPLOG ? PGB_EXPT_SIZE : 2];
   __shared__ __attribute__((aligned(16))) double s_logt[EXPLOG ? PGB_LOGT_SIZE : 2];
@@ -550,12 +571,14 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
     u += g1 - g0;
     const long long base = (long long)chunk * CH + tid * RPT;
     double yv[RPT], nv[RPT];
+    double av[CMPL ? RPT : 1];  // (compiled family: the aux column, fetched with y)
     uint32_t ysgn[RPT];  // (Bernoulli families: sign mask of the predictor, once per row instead of once per evaluation)
     uint32_t root_ids = 0;
 #pragma unroll
     for (int e = 0; e < RPT; ++e) {
       if constexpr (!MKPASS) {  // (the pass loop of the K = 2, 3, 4 instances fetches a row's inputs where it evaluates it)
         yv[e] = gy[base + e];
+        if constexpr (CMPL) av[e] = PGB_CL_AUX(base + e);
         if constexpr (YBIT) ysgn[e] = yv[e] > 0.5 ? 0u : 0x80000000u;  // Bernoulli: the response only picks the sign
         nv[e] = noi[base + e];
         if constexpr (KT == 1)
@@ -1079,6 +1102,8 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             const double smu = pgb_u2d(pgb_d2u(mu) ^ ((unsigned long long)sgn_hi << 32));
             if constexpr (PROBIT) llr = lphi_lds(smu, s_lphi);  // (= pgb_loglik_bern_s: in [-2047, 1e-16] by itself)
             else llr = pgb_loglik_bern_s(FAM, smu, &tb);
+          } else if constexpr (CMPL) {  // (plain path only: e_lin is the lane's row slot)
+            llr = PGB_CL_LL(yr, mu, av[CMPL ? e_lin : 0]);
           } else {
             llr = pgb_loglik1q(FAM >= 0 ? FAM : S.family, yr, mu, cn.inv_sigma2, cn.lik_param2, &tb);
           }
@@ -1191,6 +1216,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
         // (single output: the four rows' inputs are requested together -- the arrays are padded to whole
         //  chunks -- instead of one dependent round trip per row and evaluation)
         double yrr[RPT], noir[RPT], str_[RPT], offr[RPT];
+        double auxr[CMPL ? RPT : 1];
         const double init_leaf = S.init_leaf;
         if constexpr (!MK) {
           const double* __restrict__ const yp = S.y;
@@ -1203,6 +1229,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             noir[e] = noi0[base + e];
             str_[e] = pk[base + e].x;
             offr[e] = ho ? op[base + e] : 0.0;  // (x + 0.0 == x bit for bit)
+            if constexpr (CMPL) auxr[e] = PGB_CL_AUX(base + e);
           }
         }
 #pragma unroll
@@ -1275,6 +1302,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             const double offv = offr[e];
             auto ll1 = [&](double mu1) -> double {
               if constexpr (PROBIT) return lphi_lds(yr > 0.5 ? mu1 : -mu1, s_lphi);  // (the staged layout)
+              else if constexpr (CMPL) return PGB_CL_LL(yr, mu1, auxr[CMPL ? e : 0]);
               else return pgb_loglik1q(fam, yr, mu1, cn.inv_sigma2, cn.lik_param2, &tb);
             };
             ce[0] += quant_ll(ll1((noir[e] + offv) + init_leaf), S.sc.cl);

@@ -67,6 +67,13 @@ struct pgb_handle {
   // callback family: the host evaluates the per-row log-likelihood once per slot
   pgb_loglik_fn cb_fn;
   void* cb_ctx;
+  // compiled family (pgb_compiled_host.h): the loaded code object, its kernel, the params of the next launches
+  // (by value) and the aux column ([n_pad], zero unless pgb_set_loglik_aux set it)
+  hipModule_t cl_module;
+  hipFunction_t cl_fn;
+  int cl_nparams;
+  pgb_compiled_params cl_prm;
+  double* cl_aux;
   std::vector<double> y_host, off_host;
   std::vector<int32_t> rules_host;  // the PGB_RULE_* of the columns: every exported split node carries its own
   int device;
@@ -174,6 +181,7 @@ static ll_kernel_t select_ll_kernel(int K, bool lin, int family) {
     case PGB_FAMILY_ASYMLAPLACE: return k_loglik<1, PGB_FAMILY_ASYMLAPLACE, false>;
     case PGB_FAMILY_GAMMA_LOG: return k_loglik<1, PGB_FAMILY_GAMMA_LOG, false>;
     case PGB_FAMILY_CALLBACK: return k_loglik<1, PGB_FAMILY_CALLBACK, false>;
+    case PGB_FAMILY_COMPILED: return nullptr;  // (a module kernel: pgb_set_loglik_code)
     default: return k_loglik<1, PGB_FAMILY_STUDENT_T, false>;
   }
 }
@@ -197,10 +205,12 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
              s->family == PGB_FAMILY_BERNOULLI_LOGIT || s->family == PGB_FAMILY_POISSON_LOG ||
              s->family == PGB_FAMILY_NEGBIN_LOG || s->family == PGB_FAMILY_ASYMLAPLACE ||
              s->family == PGB_FAMILY_STUDENT_T || s->family == PGB_FAMILY_GAMMA_LOG ||
-             s->family == PGB_FAMILY_CALLBACK) {
+             s->family == PGB_FAMILY_CALLBACK || s->family == PGB_FAMILY_COMPILED) {
     if (s->n_outputs != 1) return fail(PGB_E_INVALID, "this family has a single output");
     if (s->family == PGB_FAMILY_CALLBACK && s->response != PGB_RESPONSE_CONSTANT)
       return fail(PGB_E_UNSUPPORTED, "the callback family has constant leaves");
+    if (s->family == PGB_FAMILY_COMPILED && s->response != PGB_RESPONSE_CONSTANT)
+      return fail(PGB_E_UNSUPPORTED, "the compiled family has constant leaves");
   } else {
     return fail(PGB_E_UNSUPPORTED, "unknown family");
   }
@@ -238,6 +248,11 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   }
   h->cb_fn = nullptr;
   h->cb_ctx = nullptr;
+  h->cl_module = nullptr;
+  h->cl_fn = nullptr;
+  h->cl_nparams = -1;
+  memset(&h->cl_prm, 0, sizeof h->cl_prm);
+  h->cl_aux = nullptr;
   h->out_host = h->out_dev = nullptr;
   h->st_dense = nullptr;
   h->out_valid = 0;
@@ -288,7 +303,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   // CU for probit, 3 for K = 4 -- so that no workgroup waits for another to finish; the pass aims for at
   // least as many work items.  (cfg4: 1024 -> 1280 workgroups, k_loglik 40.3 -> 37.5 us.)
   h->ll_kernel = select_ll_kernel(d.K, d.response != PGB_RESPONSE_CONSTANT, d.family);
-  if (d.family != PGB_FAMILY_NORMAL && !getenv("PGB_LL_GRID")) {
+  if (d.family != PGB_FAMILY_NORMAL && h->ll_kernel && !getenv("PGB_LL_GRID")) {
     int per_cu = 0, cus = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h->ll_kernel, BT, 0) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0) {
@@ -361,6 +376,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
     h->y_host.assign((size_t)d.n, 0.0);
     h->off_host.assign((size_t)d.n, 0.0);
   }
+  if (s->family == PGB_FAMILY_COMPILED) DA(h->cl_aux, d.n_pad);  // (zeroed below)
   DA(d.trees, d.m);
   DA(d.parts, 2 * MAXP);
   DA(d.jobs, 2 * MAXP);
@@ -434,6 +450,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   }
   HC(hipMemcpyAsync(prior_leaf, s->prior_leaf, PGB_MAX_DEPTH * sizeof(double), hipMemcpyHostToDevice, sm));
   HC(hipMemsetAsync(y, 0, d.n_pad * sizeof(double), sm));
+  if (h->cl_aux) HC(hipMemsetAsync(h->cl_aux, 0, d.n_pad * sizeof(double), sm));
   HC(hipMemsetAsync(off, 0, (size_t)d.K * d.n_pad * sizeof(double), sm));
   HC(hipMemsetAsync(pack, 0, d.n_pad * sizeof(double2), sm));
   HC(hipMemsetAsync(rs_mean, 0, (size_t)K * d.n_pad * sizeof(double), sm));
@@ -522,6 +539,7 @@ extern "C" int pgb_destroy(pgb_handle* h) {
   for (size_t i = 0; i < h->allocs.size(); ++i)
     if (h->alloc_owned[i]) (void)hipFree(h->allocs[i]);
   if (h->slab) (void)hipFree(h->slab);
+  if (h->cl_module) (void)hipModuleUnload(h->cl_module);
   g_live_handles.fetch_sub(1);
   delete h;
   return PGB_OK;
@@ -709,6 +727,7 @@ extern "C" int pgb_set_offset(pgb_handle* h, const double* offset_dev) {
   return PGB_OK;
 }
 
+static int compiled_set_params(pgb_handle* h, const double* params, int32_t n_params);  // (pgb_compiled_host.h)
 extern "C" int pgb_set_likelihood(pgb_handle* h, const double* params, int32_t n_params) {
   if (!h || !params) return fail(PGB_E_INVALID, "null argument");
   JOIN_ASYNC(h);
@@ -733,6 +752,8 @@ extern "C" int pgb_set_likelihood(pgb_handle* h, const double* params, int32_t n
     h->inv_sigma2 = params[0];
     h->lik_param2 = params[1];
     h->sigma_dirty = 1;
+  } else if (h->s.family == PGB_FAMILY_COMPILED) {
+    return compiled_set_params(h, params, n_params);
   } else if (n_params != 0) {
     return fail(PGB_E_INVALID, "this family has no parameters");
   }
@@ -767,6 +788,8 @@ static int prof_events(pgb_handle* h, int k, hipEvent_t* e0, hipEvent_t* e1) {
     else hipLaunchKernelGGL((KERN), (GRID_), dim3(THREADS_), 0, h->stream, __VA_ARGS__);          \
   } while (0)
 #define LAUNCH_K(PK_, KERN, GRID_, ...) LAUNCH_KT(PK_, KERN, GRID_, BT, __VA_ARGS__)
+
+#include "pgb_compiled_host.h"
 
 static int enqueue_slots(pgb_handle* h, int count) {
   Dev& d = h->d;
@@ -843,7 +866,10 @@ static int enqueue_slots(pgb_handle* h, int count) {
       }
     }
 #undef ROWS_ARGS
-    if (d.family != PGB_FAMILY_NORMAL)  // per-row log-likelihood of the rows this round re-labelled
+    if (d.family == PGB_FAMILY_COMPILED) {  // (the module kernel of pgb_set_loglik_code)
+      const int rc_ = compiled_launch(h, par, (int)gll.x);
+      if (rc_ != PGB_OK) return rc_;
+    } else if (d.family != PGB_FAMILY_NORMAL)  // per-row log-likelihood of the rows this round re-labelled
       LAUNCH_K(PK_LL, h->ll_kernel, gll, dd, par, (int)gll.x, (const Cmd*)d.cmd, (const Ctrl*)d.ctrl, (const Job*)d.jobs,
                (const Acc*)d.acc, (const InitAcc*)d.initacc);
     h->slot += 1;
@@ -1063,6 +1089,7 @@ static int begin_steps(pgb_handle* h, int tune, int n_steps) {
   Dev& d = h->d;
   if (!h->have_data || !h->have_y) return fail(PGB_E_INVALID, "set_data/set_response first");
   REFUSE_POISONED(h);
+  if (h->s.family == PGB_FAMILY_COMPILED && !h->cl_fn) return fail(PGB_E_INVALID, "pgb_set_loglik_code first");
   int par = (int)(h->slot & 1);
   h->out_valid = 0;
   hipLaunchKernelGGL(k_begin, dim3(1), dim3(256), 0, h->stream, h->d_dev, par, tune, n_steps,
@@ -1244,6 +1271,7 @@ extern "C" int pgb_step_async(pgb_handle* h, int32_t tune, int32_t n_steps) {
   JOIN_ASYNC(h);
   if (!h->have_data || !h->have_y) return fail(PGB_E_INVALID, "set_data/set_response first");
   REFUSE_POISONED(h);
+  if (h->s.family == PGB_FAMILY_COMPILED && !h->cl_fn) return fail(PGB_E_INVALID, "pgb_set_loglik_code first");
   h->job_running = 1;
   h->job_rc = PGB_OK;
   h->job_err[0] = 0;

@@ -45,15 +45,9 @@
 #include "pgbart_image.h"
 #include "pgbart_pack.h"
 #include "pgbart_spec.h"
+#include "pgbart_compiled.h"  // (family 11: its code object is compiled at run time, k_loglik_compiled.hip)
 
-#define CH 1024 /* rows per chunk = rows per k_rows workgroup */
-#define BT 256  /* threads per workgroup */
-#define RPT (CH / BT)
-#define MAXN PGB_MAX_NODES
-#define MAXP PGB_MAX_PARTICLES
-#define CC_ROUNDS 256
-#define NGEN 8 /* generations of particle leaf labels (ring) */
-
+#include "pgb_dims.h"
 
 // One translation unit; the parts below are included in this order (each relies on the ones above).
 #include "pgb_dev_types.h"

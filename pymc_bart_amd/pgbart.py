@@ -433,6 +433,8 @@ class PGBART(_Base):
                         backend=self._backend_arg)
         if self.likelihood.family == "callback":
             smp.set_loglik_callback(self.likelihood.logp)
+        elif self.likelihood.family == "compiled":
+            smp.set_compiled_likelihood(self.likelihood)
         return smp
 
     @property

@@ -181,6 +181,11 @@ class PySampler:
         lib, mem = self.backend.lib, self.backend.mem
         self._h = C.c_void_p()
         cs = settings.as_c()
+        # family "compiled": its code object runs in the HIP library only; any other backend runs the body's host
+        # build as family "callback" (set_compiled_likelihood) -- the same per-row values, the same sampler
+        self._compiled_on_host = settings.family == "compiled" and lib.backend_name != "hip-gfx950"
+        if self._compiled_on_host:
+            cs.family = _abi.FAMILIES["callback"]
         # (device backends: a stream object to keep alive; the CPU oracle has none)
         self._stream = mem.sampler_stream() if hasattr(mem, "sampler_stream") else None
         stream_ptr = int(self._stream.cuda_stream) if self._stream is not None else mem.stream_ptr
@@ -237,6 +242,17 @@ class PySampler:
 
     # -- likelihood parameters at the current point -------------------------------
     def set_likelihood(self, params) -> None:
+        if getattr(self, "_compiled_on_host", False):
+            # (the host build reads its params from its context between SMC rounds: the next astep sees them)
+            a = np.asarray(params, np.float64).ravel()
+            ctx = getattr(self, "_cl_ctx", None)
+            if ctx is None:
+                raise _abi.PGBError("set_compiled_likelihood first")
+            if a.size != self._cl_nparams or not np.all(np.isfinite(a)):
+                raise _abi.PGBError(f"the compiled likelihood takes {self._cl_nparams} finite params, got {a.tolist()}")
+            for i, v in enumerate(a):
+                ctx.params[i] = float(v)
+            params = []
         key = tuple(params) if isinstance(params, (list, tuple)) else None
         if key is not None and key == getattr(self, "_lik_key", None):
             return  # unchanged since the last call (sigma fixed, parameter-free families): nothing to send
@@ -275,6 +291,39 @@ class PySampler:
         self._callback_error = None
         self._callback = _abi.LOGLIK_FN(trampoline)  # keep it alive as long as the sampler
         lib.check(lib.lib.pgb_set_loglik_callback(self._h, self._callback, None), "pgb_set_loglik_callback")
+
+    def set_compiled_likelihood(self, lik) -> None:
+        """Family "compiled" (:class:`pymc_bart_amd.CompiledLikelihood`): the HIP library loads the body's code
+        object for its particle build (``pgb_set_loglik_code``) and its aux column; any other backend installs the
+        body's host build as the native log-likelihood callback (no Python per row)."""
+        from .compiled import CompiledContext
+
+        if self.settings.family != "compiled":
+            raise _abi.PGBError("the sampler was not created with the compiled family")
+        lib, mem = self.backend.lib, self.backend.mem
+        n = self.settings.n
+        if lik.aux is not None and lik.aux.size != n:
+            raise ValueError(f"aux must hold n = {n} values, got {lik.aux.size}")
+        if not self._compiled_on_host:
+            build = lik.compiled(lib.max_particles)
+            set_code, set_aux = lib.compiled_entry_points()
+            self._cl_code = C.create_string_buffer(build.code, len(build.code))
+            lib.check(set_code(self._h, C.cast(self._cl_code, C.c_void_p), len(build.code), build.n_params),
+                      "pgb_set_loglik_code")
+            self._cl_aux = None if lik.aux is None else mem.from_host(lik.aux)
+            lib.check(set_aux(self._h, None if self._cl_aux is None else mem.ptr(self._cl_aux)), "pgb_set_loglik_aux")
+        else:
+            build = lik.compiled(64)  # (the host build is the same for either particle build)
+            self._cl_aux_host = None if lik.aux is None else np.ascontiguousarray(lik.aux, np.float64)
+            ctx = CompiledContext()
+            ctx.aux = None if self._cl_aux_host is None else self._cl_aux_host.ctypes.data
+            self._cl_ctx = ctx
+            self._cl_fn = build.host_function()  # (kept alive with the sampler)
+            lib.check(lib.lib.pgb_set_loglik_callback(self._h, self._cl_fn, C.cast(C.pointer(ctx), C.c_void_p)),
+                      "pgb_set_loglik_callback")
+        self._cl_nparams = build.n_params
+        self._cl_build = build
+        self._lik_key = None
 
     # -- one astep -----------------------------------------------------------------
     def step(self, tune: bool, fetch: bool = True):

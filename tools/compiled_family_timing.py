@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""ms per astep of family "compiled" against the built-in family it spells out, and against the host callback.
+
+At cfg2 size (n = 100 k, p = 50, m = 200, P = 40; heteroscedastic Friedman response), 10 tuning asteps, then 20 timed
+asteps, each ended by a device synchronise:
+
+* ``builtin``   AsymmetricLaplace(b = 0.25, q = 0.9), the library's own k_loglik<1, 7, false>,
+* ``compiled``  the same check loss written as a body (CompiledLikelihood), its run-time code object,
+* ``callback``  the same body as a Python callback (family "callback"), at n = 10 k: too slow at full size.
+
+Also reports the compiled kernel's resource usage and compile time (on a fresh cache), and whether the two full-size
+runs' sum_trees are bit-identical.  Prints ONE JSON line.
+
+  python tools/compiled_family_timing.py [--steps 20] [--tune 10] [--compiled-only]
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+CHECK_LOSS = "double u = (y - mu) / b;  return -(u * (u < 0.0 ? q - 1.0 : q));"
+
+
+def data(n, p=50, seed=3415):
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(0, 1, (n, p))
+    f = 10 * np.sin(np.pi * X[:, 0] * X[:, 1]) + 20 * (X[:, 2] - 0.5) ** 2 + 10 * X[:, 3] + 5 * X[:, 4]
+    return X, f + rng.normal(0, 1.0 + X[:, 0], n)
+
+
+def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40):
+    import torch
+
+    from pymc_bart_amd.sampler import PyBartSettings, PySampler, default_backend
+
+    st = PyBartSettings.from_data(X, Y, m=m, num_particles=P, seed=7, family=family)
+    p = X.shape[1]
+    s = PySampler(st, X, Y, np.zeros(p, np.int32), np.ones(p), backend=default_backend())
+    params = [0.25, 0.9]
+    if lik is not None:
+        s.set_compiled_likelihood(lik)
+    if callback is not None:
+        s.set_loglik_callback(callback)
+        params = []
+    s.set_likelihood(params)
+    for _ in range(tune):
+        s.step(True, fetch=False)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        s.step(False, fetch=False)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    out = s.sum_trees_device() if hasattr(s, "sum_trees_device") else None
+    st_host = s.backend.mem.to_host(out) if out is not None else None
+    return float(np.median(ms)), float(np.mean(ms)), st_host
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--tune", type=int, default=10)
+    ap.add_argument("--compiled-only", action="store_true", help="only the full-size compiled run (under a profiler)")
+    args = ap.parse_args(argv)
+    os.environ.setdefault("PGB_JIT_CACHE", tempfile.mkdtemp(prefix="pgb_jit_timing_"))  # (a fresh cache: a real compile)
+    from pymc_bart_amd.compiled import CompiledLikelihood
+
+    t0 = time.perf_counter()
+    lik = CompiledLikelihood(CHECK_LOSS, params={"b": 0.25, "q": 0.9})
+    build = lik.compiled(64)
+    compile_s = time.perf_counter() - t0
+
+    X, Y = data(100_000)
+    if args.compiled_only:
+        c_med, c_mean, _ = run(X, Y, "compiled", args.tune, args.steps, lik=lik)
+        print(json.dumps({"metric": "ms_per_astep", "compiled_ms": round(c_med, 3), "kernel": build.resources}))
+        return 0
+    b_med, b_mean, b_st = run(X, Y, "asymmetric_laplace", args.tune, args.steps)
+    c_med, c_mean, c_st = run(X, Y, "compiled", args.tune, args.steps, lik=lik)
+
+    def check_loss(y, mu):
+        u = (y - mu) / 0.25
+        return -(u * np.where(u < 0.0, 0.9 - 1.0, 0.9))
+
+    Xs, Ys = data(10_000)
+    cb_med, cb_mean, _ = run(Xs, Ys, "callback", args.tune, args.steps, callback=check_loss)
+    cs_med, cs_mean, _ = run(Xs, Ys, "compiled", args.tune, args.steps, lik=lik)
+    line = {
+        "metric": "ms_per_astep", "config": "cfg2 quantile (n=100000 p=50 m=200 P=40), check loss b=0.25 q=0.9",
+        "tune": args.tune, "steps": args.steps,
+        "builtin_asymlaplace_ms": round(b_med, 3), "compiled_ms": round(c_med, 3),
+        "compiled_over_builtin": round(c_med / b_med, 3),
+        "n10k_callback_ms": round(cb_med, 3), "n10k_compiled_ms": round(cs_med, 3),
+        "callback_over_compiled_n10k": round(cb_med / cs_med, 1),
+        "sum_trees_bit_identical": bool(b_st is not None and c_st is not None and np.array_equal(b_st, c_st)),
+        "compile_seconds": round(compile_s, 2), "kernel": build.resources,
+        "means_ms": {"builtin": round(b_mean, 3), "compiled": round(c_mean, 3), "n10k_callback": round(cb_mean, 3),
+                     "n10k_compiled": round(cs_mean, 3)},
+    }
+    print(json.dumps(line))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

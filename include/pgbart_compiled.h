@@ -2,6 +2,10 @@
  * pgbart_compiled.h -- the "compiled" likelihood family: a per-row log-density written by the user as a
  * short C function body, compiled at run time into a k_loglik instance for gfx950 (a code object the HIP
  * library loads) and, for the CPU backends, into a host function with the pgb_loglik_fn signature.
+ * A body may also take K = 2 .. PGB_MAX_OUTPUTS linear predictors (a sampler with n_outputs = K, constant
+ * leaves): the code object is then the library's K-vector pass, k_loglik<K> (K <= 4) or k_loglik<0> (run-time
+ * K), with the body at its evaluation sites.  No CPU backend runs a K-vector body (the callback family has one
+ * output): its host build serves as a reference evaluator only.
  *
  * Kept apart from pgbart.h on purpose: pgbart.h is the ABI every backend (the CPU oracle included) exports in
  * full; the entry points below exist in the HIP library only.  A CPU backend runs the same body as family
@@ -24,6 +28,7 @@
 #define PGB_COMPILED_MAX_PARAMS 8
 #define PGB_COMPILED_MAGIC 0x43424750 /* "PGBC" */
 #define PGB_COMPILED_KERNEL "k_loglik_compiled"
+#define PGB_COMPILED_PROBE "k_loglik_compiled_probe"
 #define PGB_COMPILED_LAYOUT "pgb_compiled_layout_record"
 
 /* The layout record every compiled code object carries (a __device__ global named PGB_COMPILED_LAYOUT): the
@@ -33,7 +38,7 @@ typedef struct {
   int32_t magic;          /* PGB_COMPILED_MAGIC */
   int32_t max_particles;  /* PGB_MAX_PARTICLES */
   int32_t n_params;       /* params the body was compiled for */
-  int32_t pad;
+  int32_t n_outputs;      /* the K of the body's mu (1: a scalar mu) */
   int64_t sizeof_dev, sizeof_job, sizeof_cmd, sizeof_ctrl, sizeof_acc;
   uint64_t headers_hash;  /* PGB_HEADERS_HASH: a hash of the kernel headers (pymc_bart_amd/compiled.py) */
 } pgb_compiled_layout;
@@ -57,6 +62,11 @@ int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64_t bytes, i
 /* Optional per-row column `aux` (n doubles, device memory) the body reads as `aux`; NULL clears it (aux = 0.0).
  * Non-finite values are refused (PGB_E_INVALID) and the column is cleared. */
 int pgb_set_loglik_aux(pgb_handle* h, const double* aux_dev);
+/* Evaluate the loaded body, clamped like the sampler takes it ([-2047, 2047], NaN -> -2047), on n arbitrary rows:
+ * out[i] = f(y[i], mu[0 .. K-1][i], aux ? aux[i] : 0.0, the params of pgb_set_likelihood).  All pointers are device
+ * memory, mu is [K][n]; the call returns when out is written.  Runs the code object's kernel PGB_COMPILED_PROBE: the
+ * device's values of a body, to hold against its host build. */
+int pgb_compiled_probe(pgb_handle* h, const double* y, const double* mu, const double* aux, int64_t n, double* out);
 #ifdef __cplusplus
 }
 #endif
@@ -74,7 +84,8 @@ int pgb_set_loglik_aux(pgb_handle* h, const double* aux_dev);
  *   exp, log         pgb_exp_t, pgb_log_t             (pgbart_spec.h: table-driven, the same bits on both sides)
  *   log_ndtr         pgb_lphi_t                       (log Phi, the probit family's function)
  *   softplus         pgb_softplus_t                   (log(1 + e^x))
- *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour) */
+ *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour)
+ *   lgamma           pgb_cl_lgamma                    (log Gamma(x), x > 0: + - * / and pgb_log_t only) */
 #if defined(PGB_COMPILED_VOCABULARY) && !defined(PGB_COMPILED_VOCABULARY_ON)
 #define PGB_COMPILED_VOCABULARY_ON
 #ifndef PGB_COMPILED_VOCABULARY_FNS
@@ -90,6 +101,29 @@ PGB_HD double pgb_cl_softplus(double t, const double* expt, const double* logt) 
   if (t > 36.0) return t;
   return pgb_log_t(1.0 + pgb_exp_t(t, expt), logt);
 }
+/* log Gamma(x): x < 10 moves up by the recurrence (log Gamma(x) = log Gamma(x + j) - log(x (x + 1) .. (x + j - 1)),
+ * one logarithm of the product), then Stirling's series to the z^-11 term (truncation < 7e-16 at z >= 10).
+ * |error| < 1e-13 max(1, |log Gamma(x)|) on [1e-6, 1e12].  x <= 0 or NaN -> NaN (the row takes the lower bound),
+ * +inf -> +inf. */
+PGB_HD double pgb_cl_lgamma(double x, const double* logt) {
+  if (!(x > 0.0)) return pgb_u2d(0x7FF8000000000000ull);
+  if (x > 1.7976931348623157e308) return x;
+  double z = x, p = 1.0;
+  while (z < 10.0) {
+    p = p * z;
+    z = z + 1.0;
+  }
+  const double r = 1.0 / z, r2 = r * r;
+  double s = -1.9175269175269176e-03 * r2 + 8.4175084175084175e-04;  /* -691/360360, 1/1188 */
+  s = s * r2 - 5.9523809523809524e-04;                                  /* -1/1680 */
+  s = s * r2 + 7.9365079365079365e-04;                                  /*  1/1260 */
+  s = s * r2 - 2.7777777777777778e-03;                                  /* -1/360  */
+  s = s * r2 + 8.3333333333333333e-02;                                  /*  1/12   */
+  const double lz = pgb_log_t(z, logt);
+  double v = ((z - 0.5) * lz - z) + (9.1893853320467274e-01 + s * r);    /* + log sqrt(2 pi) */
+  if (p != 1.0) v = v - pgb_log_t(p, logt);
+  return v;
+}
 #endif
 #define exp(x) pgb_exp_t((double)(x), PGB_CL_EXPT)
 #define log(x) pgb_log_t((double)(x), PGB_CL_LOGT)
@@ -98,6 +132,7 @@ PGB_HD double pgb_cl_softplus(double t, const double* expt, const double* logt) 
 #define fabs(x) pgb_cl_fabs((double)(x))
 #define fmin(a, b) pgb_cl_fmin((double)(a), (double)(b))
 #define fmax(a, b) pgb_cl_fmax((double)(a), (double)(b))
+#define lgamma(x) pgb_cl_lgamma((double)(x), PGB_CL_LOGT)
 #endif
 #if defined(PGB_COMPILED_VOCABULARY_END) && defined(PGB_COMPILED_VOCABULARY_ON)
 #undef PGB_COMPILED_VOCABULARY_ON
@@ -110,4 +145,5 @@ PGB_HD double pgb_cl_softplus(double t, const double* expt, const double* logt) 
 #undef fabs
 #undef fmin
 #undef fmax
+#undef lgamma
 #endif

@@ -229,6 +229,13 @@ class PGBLibrary:
         lib.pgb_set_loglik_aux.restype = C.c_int
         return lib.pgb_set_loglik_code, lib.pgb_set_loglik_aux
 
+    def compiled_probe_entry_point(self):
+        """``pgb_compiled_probe`` (include/pgbart_compiled.h): the loaded body evaluated on given rows."""
+        f = self.lib.pgb_compiled_probe
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     @property
     def backend_name(self) -> str:
         return self.lib.pgb_backend_name().decode()

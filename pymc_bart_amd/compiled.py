@@ -10,8 +10,10 @@ into
   family ``"callback"`` -- natively, no Python in the per-row loop.
 
 Both sides evaluate the body with the same vocabulary (table-driven ``exp`` / ``log`` / ``log_ndtr`` /
-``softplus`` of ``include/pgbart_spec.h`` and explicit comparisons), so that a CPU backend checks the GPU chain bit
-for bit.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
+``softplus`` / ``lgamma`` on the tables of ``include/pgbart_spec.h``, explicit comparisons), so that a CPU backend
+checks the GPU chain bit for bit.  A body of ``n_outputs = K >= 2`` reads ``mu[0] .. mu[K-1]``: its code object is the
+library's K-vector pass; no CPU backend runs it (the callback family has one output), and its host build is an
+evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is held to.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
 everything that goes into them.
 """
 
@@ -25,6 +27,7 @@ import re
 import subprocess
 import tempfile
 import time
+import warnings
 
 import numpy as np
 
@@ -48,6 +51,7 @@ GENCO_FLAGS = ["--genco", "--no-gpu-bundle-output"]
 HOST_FLAGS = ["-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared"]
 
 MAX_PARAMS = 8
+MAX_OUTPUTS = 16  # PGB_MAX_OUTPUTS
 #: what a body may call (include/pgbart_compiled.h, section "vocabulary")
 VOCABULARY = {
     "exp": "exp(x): pgb_exp_t, the spec's table-driven exponential",
@@ -57,8 +61,9 @@ VOCABULARY = {
     "fabs": "fabs(x): x < 0 ? -x : x + 0.0",
     "fmin": "fmin(a, b): a < b ? a : b",
     "fmax": "fmax(a, b): a > b ? a : b",
+    "lgamma": "lgamma(x): log Gamma(x) for x > 0 (NaN otherwise), on the log table",
 }
-_EXPLOG = ("exp", "log", "softplus")
+_EXPLOG = ("exp", "log", "softplus", "lgamma")
 _C_KEYWORDS = {
     "auto", "break", "case", "char", "const", "continue", "default", "do", "double", "else", "enum", "extern",
     "float", "for", "goto", "if", "inline", "int", "long", "register", "restrict", "return", "short", "signed",
@@ -89,10 +94,17 @@ def _strip_comments(body: str) -> str:
     return re.sub(r"//[^\n]*", "", body)
 
 
-def validate(body: str, param_names) -> tuple[str, ...]:
+def check_outputs(n_outputs) -> int:
+    if isinstance(n_outputs, bool) or int(n_outputs) != n_outputs or not 1 <= int(n_outputs) <= MAX_OUTPUTS:
+        raise ValueError(f"n_outputs must be an integer in [1, {MAX_OUTPUTS}], got {n_outputs!r}")
+    return int(n_outputs)
+
+
+def validate(body: str, param_names, n_outputs: int = 1) -> tuple[str, ...]:
     """Refuse, before any compiler runs, what the body may not contain.  Returns the param names as a tuple."""
     if not isinstance(body, str) or not body.strip():
         raise ValueError("the body must be a non-empty string of C statements")
+    K = check_outputs(n_outputs)
     names = tuple(param_names)
     if len(names) > MAX_PARAMS:
         raise ValueError(f"at most {MAX_PARAMS} params, {len(names)} given")
@@ -102,6 +114,8 @@ def validate(body: str, param_names) -> tuple[str, ...]:
             raise ValueError(f"param name {nm!r} is not a C identifier")
         if nm in ("y", "mu", "aux"):
             raise ValueError(f"param name {nm!r} clashes with the body's arguments y, mu, aux")
+        if K > 1 and nm == "K":
+            raise ValueError("param name 'K' is reserved: a body of n_outputs >= 2 reads its number of outputs as K")
         if nm in VOCABULARY:
             raise ValueError(f"param name {nm!r} clashes with the vocabulary ({', '.join(VOCABULARY)})")
         if nm in _C_KEYWORDS:
@@ -151,11 +165,23 @@ def validate(body: str, param_names) -> tuple[str, ...]:
         lineno = code.count("\n", 0, m.start()) + 1
         raise CompileError(f"line {lineno}: {fn!r} is not in the likelihood vocabulary:\n    "
                            f"{body.splitlines()[lineno - 1].strip()}\nthe vocabulary: {vocabulary_text()}")
+    if K > 1:
+        for m in re.finditer(r"\bmu\b(\s*\[\s*([0-9]+)\s*\])?", code):
+            lineno = code.count("\n", 0, m.start()) + 1
+            src = body.splitlines()[lineno - 1].strip()
+            if m.group(1) is None and not re.match(r"\s*\[", code[m.end():]):
+                raise CompileError(f"line {lineno}: mu holds K = {K} predictors, it is not a scalar: write mu[0] .. "
+                                   f"mu[{K - 1}]\n    {src}")
+            if m.group(2) is not None and int(m.group(2)) >= K:
+                raise ValueError(f"line {lineno}: mu[{m.group(2)}] is out of range: mu holds K = {K} predictors "
+                                 f"(mu[0] .. mu[{K - 1}])\n    {src}")
+        for m in re.finditer(r"\b(?:int|double|float|long|short|char|unsigned|signed)\s+K\b", code):
+            raise ValueError("'K' is reserved: a body of n_outputs >= 2 reads its number of outputs as K")
     return names
 
 
 def uses_tables(body: str) -> bool:
-    """Whether the body calls exp / log / softplus (the kernel then stages their tables in LDS)."""
+    """Whether the body calls exp / log / softplus / lgamma (the kernel then stages their tables in LDS)."""
     code = _strip_comments(body)
     return any(re.search(rf"\b{f}\s*\(", code) for f in _EXPLOG)
 
@@ -197,9 +223,10 @@ def cache_dir() -> str:
     return os.environ.get("PGB_JIT_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "pymc_bart_amd", "jit")
 
 
-def cache_key(body: str, param_names, max_particles: int = 64) -> str:
+def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1) -> str:
     h = hashlib.sha256()
     h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
+                         "n_outputs": int(n_outputs),
                          "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
                          "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
                         sort_keys=True).encode())
@@ -220,9 +247,10 @@ def _write_atomic(path: str, data: bytes) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------- the builds
-def _body_defs(names, max_particles: int, explog: bool) -> str:
+def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1) -> str:
     return "\n".join([
         f"#define PGB_COMPILED_NPARAMS {len(names)}",
+        f"#define PGB_COMPILED_NOUT {int(n_outputs)}",
         f"#define PGB_COMPILED_EXPLOG {1 if explog else 0}",
         f"#define PGB_HEADERS_HASH {headers_hash()}ull",
         "#define PGB_COMPILED_PARAMS " + "".join(f", const double {nm}" for nm in names),
@@ -235,9 +263,12 @@ def _body_text(body: str) -> str:
     return '#line 1 "loglik body"\n' + body + "\n"
 
 
-def _host_source(body: str, names) -> str:
+def _host_source(body: str, names, n_outputs: int = 1) -> str:
     params = "".join(f", const double {nm}" for nm in names)
     args = "".join(f", c->params[{i}]" for i in range(len(names)))
+    K = int(n_outputs)
+    if K > 1:
+        return _host_source_k(body, params, args, K)
     return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood body */
 #include <stdint.h>
 #include <stddef.h>
@@ -261,6 +292,42 @@ typedef struct {{
 int pgb_compiled_loglik(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out) {{
   const pgb_compiled_ctx* c = (const pgb_compiled_ctx*)ctx;
   for (int64_t i = 0; i < n; ++i) out[i] = pgb_compiled_user(y[i], mu[i], c->aux ? c->aux[row[i]] : 0.0{args});
+  return 0;
+}}
+"""
+
+
+def _host_source_k(body: str, params: str, args: str, K: int) -> str:
+    """The host build of a K-vector body: no sampler runs it (no CPU backend has a K-vector callback family), it
+    evaluates given rows -- the reference the device's probe kernel is held to."""
+    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood body of {K} outputs */
+#include <stdint.h>
+#include <stddef.h>
+#define PGB_COMPILED_NO_ENTRY_POINTS
+#include "pgbart_spec.h"
+#include "pgbart_compiled.h"
+#define PGB_CL_EXPT pgb_tab_exp()
+#define PGB_CL_LOGT pgb_tab_log()
+#define PGB_CL_LPHI pgb_tab_lphi()
+#define PGB_COMPILED_VOCABULARY
+#include "pgbart_compiled.h"
+static double pgb_compiled_user(double y, const double* mu, double aux{params}) {{
+  enum {{ K = {K} }};
+{_body_text(body)}}}
+#define PGB_COMPILED_VOCABULARY_END
+#include "pgbart_compiled.h"
+typedef struct {{
+  const double* aux;
+  double params[PGB_COMPILED_MAX_PARAMS];
+}} pgb_compiled_ctx;
+/* out[i] = the body at (y[i], mu[0 .. K-1][i] ([K][n]), aux[i] or 0.0), clamped like the sampler takes it */
+int pgb_compiled_eval_rows(void* ctx, const double* y, const double* mu, int64_t n, double* out) {{
+  const pgb_compiled_ctx* c = (const pgb_compiled_ctx*)ctx;
+  for (int64_t i = 0; i < n; ++i) {{
+    double m[{K}];
+    for (int k = 0; k < {K}; ++k) m[k] = mu[(size_t)k * (size_t)n + (size_t)i];
+    out[i] = pgb_clamp_loglik(pgb_compiled_user(y[i], m, c->aux ? c->aux[i] : 0.0{args}));
+  }}
   return 0;
 }}
 """
@@ -290,7 +357,7 @@ def kernel_resources(code_object_path: str) -> dict:
     end = notes.index("\n...", start) if "\n..." in notes[start:] else len(notes)
     meta = yaml.safe_load(notes[start:end])
     for k in meta["amdhsa.kernels"]:
-        if k[".name"] == "k_loglik_compiled":
+        if k[".name"] == "k_loglik_compiled":  # (not the probe: its resources do not matter)
             vg, ag = int(k[".vgpr_count"]), int(k.get(".agpr_count", 0))
             lds = int(k[".group_segment_fixed_size"])
             unified = ((vg + 3) // 4) * 4 + ag
@@ -308,8 +375,10 @@ class CompiledLoglik:
     """One build of a body: the code object (``code``), the host library (``host_lib``), the kernel's resource
     usage (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit."""
 
-    def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached):
+    def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached,
+                 n_outputs=1):
         self.key, self.body, self.param_names, self.max_particles = key, body, tuple(param_names), int(max_particles)
+        self.n_outputs = int(n_outputs)
         self.code, self.host_lib, self.resources = code, host_lib, resources
         self.compile_seconds, self.cached = compile_seconds, cached
         self._host = None
@@ -322,9 +391,41 @@ class CompiledLoglik:
         """The host build's ``pgb_compiled_loglik`` as a ctypes function (``pgb_loglik_fn``)."""
         from . import _abi
 
+        if self.n_outputs > 1:
+            raise CompileError(f"a body of {self.n_outputs} outputs has no callback: no CPU backend runs a K-vector "
+                               "compiled likelihood (see host_eval)")
         if self._host is None:
             self._host = _abi.LOGLIK_FN(("pgb_compiled_loglik", C.CDLL(self.host_lib)))
         return self._host
+
+    def host_eval(self, y, mu, aux=None, params=()):
+        """The host build of a K-vector body on given rows: ``mu`` is [K][n]; the values are clamped like the
+        sampler takes them ([-2047, 2047], NaN -> -2047)."""
+        if self.n_outputs < 2:
+            raise CompileError("host_eval is the evaluator of a K-vector body (n_outputs >= 2)")
+        y = np.ascontiguousarray(y, np.float64).ravel()
+        n = y.size
+        mu = np.ascontiguousarray(mu, np.float64)
+        if mu.shape != (self.n_outputs, n):
+            raise ValueError(f"mu must be [K][n] = ({self.n_outputs}, {n}), got {mu.shape}")
+        ctx = CompiledContext()
+        keep = None
+        if aux is not None:
+            keep = np.ascontiguousarray(aux, np.float64).ravel()
+            if keep.size != n:
+                raise ValueError(f"aux must hold n = {n} values")
+            ctx.aux = keep.ctypes.data
+        for i, v in enumerate(params):
+            ctx.params[i] = float(v)
+        if self._host is None:
+            f = C.CDLL(self.host_lib).pgb_compiled_eval_rows
+            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+            self._host = f
+        out = np.empty(n)
+        rc = self._host(C.cast(C.pointer(ctx), C.c_void_p), y.ctypes.data, mu.ctypes.data, n, out.ctypes.data)
+        if rc != 0:
+            raise CompileError(f"pgb_compiled_eval_rows returned {rc}")
+        return out
 
 
 class CompiledContext(C.Structure):
@@ -333,12 +434,21 @@ class CompiledContext(C.Structure):
     _fields_ = [("aux", C.c_void_p), ("params", C.c_double * MAX_PARAMS)]
 
 
-def compile_loglik(body: str, param_names=(), max_particles: int = 64) -> CompiledLoglik:
+def _warn_scratch(b: "CompiledLoglik") -> None:
+    if b.n_outputs > 1 and b.resources.get("scratch_bytes", 0) > 0:
+        warnings.warn(f"the likelihood body of {b.n_outputs} outputs puts {b.resources['scratch_bytes']} B per thread "
+                      "in scratch memory: mu lives in registers, and a run-time index such as mu[(int)y] moves it "
+                      "out.  Pick by comparison instead -- for (int k = 0; k < K; ++k) if (k == c) m = mu[k]; -- "
+                      "which is what the built-in softmax does", RuntimeWarning, stacklevel=3)
+
+
+def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1) -> CompiledLoglik:
     """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
-    (64 or 128) -- or take it from the cache."""
-    names = validate(body, param_names)
+    (64 or 128) and ``n_outputs`` predictors -- or take it from the cache."""
+    K = check_outputs(n_outputs)
+    names = validate(body, param_names, K)
     mp = 128 if int(max_particles) > 64 else 64
-    key = cache_key(body, names, mp)
+    key = cache_key(body, names, mp, K)
     root = cache_dir()
     os.makedirs(root, exist_ok=True)
     co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
@@ -347,20 +457,22 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64) -> Compil
             meta = json.load(fh)
         with open(co_path, "rb") as fh:
             code = fh.read()
-        return CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True)
+        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K)
+        _warn_scratch(b)
+        return b
     t0 = time.perf_counter()
     with tempfile.TemporaryDirectory(prefix="pgb_jit_") as tmp:
         # host first: quick, and the compiler's messages about the body are the same on either side
         src = os.path.join(tmp, "host.c")
         with open(src, "w") as fh:
-            fh.write(_host_source(body, names))
+            fh.write(_host_source(body, names, K))
         so_tmp = os.path.join(tmp, "host.so")
         r = subprocess.run(["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", src,
                             "-o", so_tmp, "-lm"], capture_output=True, text=True)
         if r.returncode != 0:
             raise _compile_error(r.stderr, body, "host")
         with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
-            fh.write(_body_defs(names, mp, uses_tables(body)))
+            fh.write(_body_defs(names, mp, uses_tables(body), K))
         with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
             fh.write(_body_text(body))
         co_tmp = os.path.join(tmp, "k.co")
@@ -377,10 +489,12 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64) -> Compil
             host = fh.read()
     _write_atomic(co_path, code)
     _write_atomic(so_path, host)
-    meta = {"body": body, "params": list(names), "max_particles": mp, "resources": resources,
+    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "resources": resources,
             "compile_seconds": seconds}
     _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
-    return CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False)
+    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K)
+    _warn_scratch(b)
+    return b
 
 
 class CompiledLikelihood:
@@ -388,7 +502,9 @@ class CompiledLikelihood:
 
     ``body`` is the inside of ``double f(double y, double mu, double aux, const double <param>...)``:
 
-    * ``y``   the observed value of the row, ``mu`` its linear predictor (sum of trees plus offset),
+    * ``y``   the observed value of the row, ``mu`` its linear predictor (sum of trees plus offset) -- with
+      ``n_outputs = K >= 2`` the K predictors ``mu[0] .. mu[K-1]`` (``K`` is a constant the body can read; the
+      variable then has shape ``(K, n)``),
     * ``aux`` the row's entry of the optional per-row column ``aux`` (0.0 without one),
     * one ``const double`` per entry of ``params`` (at most 8), in the order given.
 
@@ -396,8 +512,8 @@ class CompiledLikelihood:
     parameters: a number, a shared variable, a callable, or a key of the point).
 
     The vocabulary: IEEE ``+ - * /``, comparisons, ``?:``, ``if``, local ``double`` and ``int`` variables, and
-    ``exp``, ``log`` (the spec's table functions), ``log_ndtr`` (log Phi), ``softplus`` (log(1 + e^x)), ``fabs``,
-    ``fmin``, ``fmax`` (explicit comparisons).  Nothing from libm (no ``sqrt``, ``pow``): the same body must give the
+    ``exp``, ``log`` (the spec's table functions), ``log_ndtr`` (log Phi), ``softplus`` (log(1 + e^x)), ``lgamma``
+    (log Gamma on the log table), ``fabs``, ``fmin``, ``fmax`` (explicit comparisons).  Nothing from libm (no ``sqrt``, ``pow``): the same body must give the
     same bits on the GPU and on the CPU.  No preprocessor lines, no ``asm``, no ``__``-names.
 
     The value is clamped to [-2047, 2047] (NaN -> -2047) and summed in fixed point exactly like family
@@ -409,10 +525,11 @@ class CompiledLikelihood:
 
     family = "compiled"
 
-    def __init__(self, body: str, params=None, aux=None):
+    def __init__(self, body: str, params=None, aux=None, n_outputs: int = 1):
         self.body = body
+        self.n_outputs = check_outputs(n_outputs)
         self.param_spec = dict(params or {})
-        self.param_names = validate(body, list(self.param_spec))
+        self.param_names = validate(body, list(self.param_spec), self.n_outputs)
         self.aux = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).ravel()
         if self.aux is not None and not np.all(np.isfinite(self.aux)):
             raise ValueError("aux must be finite")
@@ -422,7 +539,7 @@ class CompiledLikelihood:
     def compiled(self, max_particles: int = 64) -> CompiledLoglik:
         mp = 128 if int(max_particles) > 64 else 64
         if mp not in self._builds:
-            self._builds[mp] = compile_loglik(self.body, self.param_names, mp)
+            self._builds[mp] = compile_loglik(self.body, self.param_names, mp, self.n_outputs)
         return self._builds[mp]
 
     def params(self, point=None):
@@ -431,7 +548,7 @@ class CompiledLikelihood:
         return [_from_point(v, point) for v in self.param_spec.values()]
 
     def __getstate__(self):
-        return {"body": self.body, "params": self.param_spec, "aux": self.aux}
+        return {"body": self.body, "params": self.param_spec, "aux": self.aux, "n_outputs": self.n_outputs}
 
     def __setstate__(self, d):
-        self.__init__(d["body"], d["params"], d["aux"])
+        self.__init__(d["body"], d["params"], d["aux"], d.get("n_outputs", 1))

@@ -178,16 +178,27 @@ __device__ __forceinline__ long long quant_ll(double ll, double cl) {
 // object is k_loglik_compiled.hip, which includes this header with PGB_COMPILED_LOGLIK defined and a generated
 // pgb_compiled_eval(y, mu, aux, params, tables) in front of it.  There k_loglik is the __forceinline__ body of the
 // kernel k_loglik_compiled, with two arguments more: the aux column ([n_pad], like y) and the params (by value).
+// A body of K >= 2 outputs (PGB_COMPILED_NOUT) takes mu as the K-array of the K-vector sites (PGB_CL_LLK); the
+// one-output sites are then never instantiated, and vice versa.
 #ifdef PGB_COMPILED_LOGLIK
 #define PGB_LL_ENTRY(WGS) __device__ __forceinline__
 #define PGB_LL_EXTRA_ARGS , const double* __restrict__ cl_aux, const pgb_compiled_params cl_prm
 #define PGB_CL_AUX(row) cl_aux[row]
+#define PGB_CL_AUXP cl_aux
+#if PGB_COMPILED_NOUT == 1
 #define PGB_CL_LL(y, mu, aux) pgb_compiled_eval((y), (mu), (aux), cl_prm, &tb)
+#define PGB_CL_LLK(y, mu, aux) 0.0
+#else
+#define PGB_CL_LL(y, mu, aux) 0.0
+#define PGB_CL_LLK(y, mu, aux) pgb_compiled_eval((y), (mu), (aux), cl_prm, &tb)
+#endif
 #else
 #define PGB_LL_ENTRY(WGS) __global__ __launch_bounds__(BT, WGS)
 #define PGB_LL_EXTRA_ARGS
 #define PGB_CL_AUX(row) 0.0
+#define PGB_CL_AUXP nullptr
 #define PGB_CL_LL(y, mu, aux) 0.0
+#define PGB_CL_LLK(y, mu, aux) 0.0
 #endif
 #ifndef PGB_COMPILED_EXPLOG
 #define PGB_COMPILED_EXPLOG 1 /* the compiled body calls exp / log / softplus: stage their tables in LDS */
@@ -259,8 +270,10 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
   // exp / log (2.3 KB) for every instance whose family uses them
   constexpr bool PROBIT = KT == 1 && FAM == PGB_FAMILY_BERNOULLI_PROBIT;
   constexpr bool CMPL = KT == 1 && FAM == PGB_FAMILY_COMPILED;  // (plain path, aux column, params in registers)
+  constexpr bool CMPLK = MK && FAM == PGB_FAMILY_COMPILED;       // (K-vector: the pass loop, aux read next to y)
   constexpr bool EXPLOG = !(KT == 1 && (FAM == PGB_FAMILY_BERNOULLI_PROBIT || FAM == PGB_FAMILY_ASYMLAPLACE ||
-                                        FAM == PGB_FAMILY_CALLBACK)) && (!CMPL || PGB_COMPILED_EXPLOG);
+                                        FAM == PGB_FAMILY_CALLBACK)) &&
+                          (FAM != PGB_FAMILY_COMPILED || PGB_COMPILED_EXPLOG);
   __shared__ __attribute__((aligned(16))) double s_lphi[PROBIT ? PGB_LPHI_SIZE : 2];
   __shared__ __attribute__((aligned(16))) double s_expt[EXPLOG ? PGB_EXPT_SIZE : 2];
   __shared__ __attribute__((aligned(16))) double s_logt[EXPLOG ? PGB_LOGT_SIZE : 2];
@@ -597,6 +610,8 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
       // the chunk's streams as wave-uniform bases (scalar registers) + a 32-bit row offset: the loads of a row's
       // inputs then cost one shared offset instead of a 64-bit address computation each
       const gptr<const double> gy_c = gy + cbase;
+      gptr<const double> ax_c = nullptr;  // (compiled family: the aux column, read with y)
+      if constexpr (CMPLK) ax_c = as_global((const double*)PGB_CL_AUXP) + cbase;
       gptr<const double> noi_c[KB], off_c[KB];
 #pragma unroll
       for (int k = 0; k < KB; ++k) {
@@ -627,6 +642,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
       constexpr bool OWN = KT > 0;
       // (softmax: own_y holds a_c, own_nk the E_k, own_cls the class -- the row part of the factorised form)
       double own_y[OWN ? RPT : 1], own_nk[OWN ? RPT : 1][OWN ? KB : 1];
+      double own_ax[OWN && CMPLK ? RPT : 1];
       uint32_t own_cls = 0;  // (the four rows' classes, a byte each)
       bool own_have = false;
       // the label words of particle g + 1 are requested before particle g's passes (each of which is hundreds of
@@ -723,6 +739,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
               for (int e = 0; e < RPT; ++e) {
                 const uint32_t ro = (uint32_t)(tid * RPT + e) * 8u;
                 own_y[e] = gload_d_off(gy_c, ro);
+                if constexpr (CMPLK) own_ax[e] = gload_d_off(ax_c, ro);
 #pragma unroll
                 for (int k = 0; k < KB; ++k) {
                   const double nk = gload_d_off(noi_c[k], ro);
@@ -758,6 +775,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             uint32_t side, ro;  // (ro: the row's byte offset in its chunk -- what the run-time-K evaluation reads with)
             int cls;            // softmax: the observed class (y then holds a_c and nk the E_k: the row part)
             double y, nk[KB];
+            double aux[CMPLK ? 1 : 0];  // compiled family: the row's aux value
           };
           auto fetch = [&](int ps) -> PassIn {
             PassIn in;
@@ -776,6 +794,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             }
             in.y = 0.0;
             in.cls = 0;
+            if constexpr (CMPLK) in.aux[0] = 0.0;
             in.ro = r * 8u;  // (r < 1024)
 #pragma unroll
             for (int k = 0; k < KB; ++k) in.nk[k] = 0.0;
@@ -786,6 +805,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
                   if (e == ps) {
                     in.y = own_y[e];
                     if constexpr (CATF) in.cls = (int)((own_cls >> (8 * e)) & 255u);
+                    if constexpr (CMPLK) in.aux[0] = own_ax[e];
 #pragma unroll
                     for (int k = 0; k < KB; ++k) in.nk[k] = own_nk[e][k];
                   }
@@ -824,6 +844,7 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
                 }
               } else {
                 in.y = gload_d_off(gy_c, in.ro);
+                if constexpr (CMPLK) in.aux[0] = gload_d_off(ax_c, in.ro);
 #pragma unroll
                 for (int k = 0; k < KB; ++k)
                   if (k < K) {  // (wave-uniform)
@@ -887,7 +908,8 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
                     mu[k] = cur.nk[k] + vk;
                   }
                 }
-                if constexpr (KT > 0) llv = loglik_mk<KT, FAMK>(S.family, K, cur.y, mu, &tb);
+                if constexpr (CMPLK) llv = PGB_CL_LLK(cur.y, mu, cur.aux[0]);
+                else if constexpr (KT > 0) llv = loglik_mk<KT, FAMK>(S.family, K, cur.y, mu, &tb);
                 else llv = loglik_arr<KB>(S.family, K, cur.y, mu, &tb);
               }
               long long q = quant_ll(llv, cl);
@@ -1290,6 +1312,10 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
                 ce[0] += quant_ll(pgb_cat_value(ac, 0.0, Esum, tb.logt), S.sc.cl);
                 if constexpr (KT > 0) ce[1] += quant_ll(loglik_mk<KT, FAMK>(S.family, Kn, yr, mc, &tb), S.sc.cl);
                 else ce[1] += quant_ll(loglik_arr<KB>(S.family, Kn, yr, mc, &tb), S.sc.cl);
+              } else if constexpr (CMPLK) {
+                const double ax = PGB_CL_AUX(row);
+                ce[0] += quant_ll(PGB_CL_LLK(yr, ms, ax), S.sc.cl);
+                ce[1] += quant_ll(PGB_CL_LLK(yr, mc, ax), S.sc.cl);
               } else if constexpr (KT > 0) {
                 ce[0] += quant_ll(loglik_mk<KT, FAMK>(S.family, Kn, yr, ms, &tb), S.sc.cl);
                 ce[1] += quant_ll(loglik_mk<KT, FAMK>(S.family, Kn, yr, mc, &tb), S.sc.cl);

@@ -1,14 +1,18 @@
 // k_loglik_compiled.hip -- the code object of the compiled likelihood family (include/pgbart_compiled.h).
 //
 // Not part of libpgbart_hip.so: pymc_bart_amd/compiled.py compiles this unit at run time with the library's device
-// flags plus --genco, once per (body, param names, particle build), next to two generated files in its build
-// directory:
+// flags plus --genco, once per (body, param names, outputs, particle build), next to two generated files in its
+// build directory:
 //   pgb_compiled_body.inc       PGB_COMPILED_PARAMS (", const double <name>" per param), PGB_COMPILED_ARGS(P)
-//                               (", (P).v[i]" per param), PGB_COMPILED_NPARAMS, PGB_COMPILED_EXPLOG, PGB_HEADERS_HASH
+//                               (", (P).v[i]" per param), PGB_COMPILED_NPARAMS, PGB_COMPILED_NOUT (K),
+//                               PGB_COMPILED_EXPLOG, PGB_HEADERS_HASH
 //   pgb_compiled_body_text.inc  the user's body, behind a #line directive (compiler messages quote the user's lines)
-// The kernel is k_loglik<1, PGB_FAMILY_COMPILED, false> -- the library's one-output, constant-leaf pass, plain
-// (not dense) path -- with the generated function at every place where a one-output family is evaluated, and the
-// layout record the library checks before the first launch (pgb_set_loglik_code).
+// The kernel is the library's constant-leaf pass with the generated function at every place where the family is
+// evaluated: k_loglik<1, PGB_FAMILY_COMPILED, false> (plain, not dense, path) for one output; for K outputs the
+// K-vector pass of the same K as the built-in families -- k_loglik<K> for K = 2, 3, 4 (loops unrolled), k_loglik<0>
+// (run-time K) above -- at the built-in instance's occupancy.  Next to it: the layout record the library checks
+// before the first launch (pgb_set_loglik_code), and a probe kernel that evaluates the body on given rows
+// (pgb_compiled_probe).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -22,6 +26,12 @@
 
 #include "pgb_dims.h"
 #include "pgb_compiled_body.inc"
+#ifndef PGB_COMPILED_NOUT
+#define PGB_COMPILED_NOUT 1
+#endif
+#if PGB_COMPILED_NOUT < 1 || PGB_COMPILED_NOUT > PGB_MAX_OUTPUTS
+#error "PGB_COMPILED_NOUT must be in [1, PGB_MAX_OUTPUTS]"
+#endif
 
 #define PGB_COMPILED_LOGLIK 1
 #include "pgb_dev_types.h"
@@ -35,8 +45,16 @@
 #define PGB_CL_LPHI (pgb_cl_tb->lphi)
 #define PGB_COMPILED_VOCABULARY
 #include "pgbart_compiled.h"
-__device__ __forceinline__ double pgb_compiled_user(const pgb_lltabs* __restrict__ pgb_cl_tb, double y, double mu,
-                                                    double aux PGB_COMPILED_PARAMS) {
+#if PGB_COMPILED_NOUT == 1
+typedef double pgb_compiled_mu;
+#else
+typedef const double* pgb_compiled_mu;  // (the kernel's register array of the K predictors)
+#endif
+__device__ __forceinline__ double pgb_compiled_user(const pgb_lltabs* __restrict__ pgb_cl_tb, double y,
+                                                    pgb_compiled_mu mu, double aux PGB_COMPILED_PARAMS) {
+#if PGB_COMPILED_NOUT > 1
+  enum { K = PGB_COMPILED_NOUT };
+#endif
 #include "pgb_compiled_body_text.inc"
 }
 #define PGB_COMPILED_VOCABULARY_END
@@ -46,21 +64,55 @@ __device__ __forceinline__ double pgb_compiled_user(const pgb_lltabs* __restrict
 #undef PGB_CL_LPHI
 
 // the per-row value as the callback family takes it: clamped to [-2047, 2047], NaN -> -2047 (pgb_clamp_loglik)
-__device__ __forceinline__ double pgb_compiled_eval(double y, double mu, double aux, const pgb_compiled_params& p,
-                                                    const pgb_lltabs* tb) {
+__device__ __forceinline__ double pgb_compiled_eval(double y, pgb_compiled_mu mu, double aux,
+                                                    const pgb_compiled_params& p, const pgb_lltabs* tb) {
   return PGB_CLAMP_LL(pgb_compiled_user(tb, y, mu, aux PGB_COMPILED_ARGS(p)), 2047.0);
 }
 
 #include "k_loglik.h"
 
-extern "C" __global__ __launch_bounds__(BT, 3)
+#if PGB_COMPILED_NOUT == 1
+#define PGB_CL_KT 1
+#define PGB_CL_WGS 3
+#elif PGB_COMPILED_NOUT <= 4
+#define PGB_CL_KT PGB_COMPILED_NOUT
+#define PGB_CL_WGS PGB_LLK_WGS
+#else
+#define PGB_CL_KT 0
+#define PGB_CL_WGS 2
+#endif
+
+extern "C" __global__ __launch_bounds__(BT, PGB_CL_WGS)
 void k_loglik_compiled(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restrict__ cmds,
                        const Ctrl* __restrict__ ctrls, const Job* __restrict__ jobs_all, const Acc* __restrict__ acc_all,
                        const InitAcc* __restrict__ ias, const double* __restrict__ aux, const pgb_compiled_params prm) {
-  k_loglik<1, PGB_FAMILY_COMPILED, false>(Sp, par, nwg, cmds, ctrls, jobs_all, acc_all, ias, aux, prm);
+  k_loglik<PGB_CL_KT, PGB_FAMILY_COMPILED, false>(Sp, par, nwg, cmds, ctrls, jobs_all, acc_all, ias, aux, prm);
+}
+
+// pgb_compiled_probe: out[i] = the clamped body at (y[i], mu[0..K-1][i], aux[i] or 0.0, prm), i < n; the tables
+// are read from global memory (the same values the pass stages in LDS)
+extern "C" __global__ __launch_bounds__(BT)
+void k_loglik_compiled_probe(const double* __restrict__ y, const double* __restrict__ mu,
+                             const double* __restrict__ aux, long long n, const pgb_compiled_params prm,
+                             double* __restrict__ out) {
+  pgb_lltabs tb;
+  tb.lphi = pgb_tab_lphi();
+  tb.expt = pgb_tab_exp();
+  tb.logt = pgb_tab_log();
+  for (long long i = (long long)blockIdx.x * BT + threadIdx.x; i < n; i += (long long)gridDim.x * BT) {
+    const double ax = aux ? aux[i] : 0.0;
+#if PGB_COMPILED_NOUT == 1
+    out[i] = pgb_compiled_eval(y[i], mu[i], ax, prm, &tb);
+#else
+    double m[PGB_COMPILED_NOUT];
+#pragma unroll
+    for (int k = 0; k < PGB_COMPILED_NOUT; ++k) m[k] = mu[(size_t)k * n + i];
+    out[i] = pgb_compiled_eval(y[i], m, ax, prm, &tb);
+#endif
+  }
 }
 
 extern "C" __device__ pgb_compiled_layout pgb_compiled_layout_record = {
-    PGB_COMPILED_MAGIC, PGB_MAX_PARTICLES, PGB_COMPILED_NPARAMS, 0,
+    PGB_COMPILED_MAGIC, PGB_MAX_PARTICLES, PGB_COMPILED_NPARAMS, PGB_COMPILED_NOUT,
     (int64_t)sizeof(Dev), (int64_t)sizeof(Job), (int64_t)sizeof(Cmd), (int64_t)sizeof(Ctrl), (int64_t)sizeof(Acc),
     (uint64_t)PGB_HEADERS_HASH};

@@ -11,6 +11,7 @@ static void compiled_size_grid(pgb_handle* h) {
   int per_cu = 0, cus = 0;
   if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->cl_fn, BT, 0) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0) {
+    if (h->d.K >= 2 && h->d.K <= 4 && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;  // (as the built-in K = 2, 3, 4)
     long long g = (long long)per_cu * cus;
     if (g < 256) g = 256;
     if (g > 2048) g = 2048;
@@ -40,6 +41,7 @@ extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64
   }
   // the layout record: read, never launched
   const char* why = nullptr;
+  char why_k[128];
   pgb_compiled_layout rec;
   memset(&rec, 0, sizeof rec);
   hipDeviceptr_t gp = nullptr;
@@ -61,9 +63,16 @@ extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64
     why = "the code object was compiled from other kernel headers than this library";
   else if (rec.n_params != n_params)
     why = "n_params differs from the params the code object was compiled for";
-  hipFunction_t fn = nullptr;
+  else if (rec.n_outputs != h->s.n_outputs) {
+    snprintf(why_k, sizeof why_k, "the code object was compiled for %d outputs, the sampler has n_outputs = %d",
+             (int)rec.n_outputs, (int)h->s.n_outputs);
+    why = why_k;
+  }
+  hipFunction_t fn = nullptr, probe = nullptr;
   if (!why && hipModuleGetFunction(&fn, mod, PGB_COMPILED_KERNEL) != hipSuccess)
     why = "the code object has no kernel " PGB_COMPILED_KERNEL;
+  if (!why && hipModuleGetFunction(&probe, mod, PGB_COMPILED_PROBE) != hipSuccess)
+    why = "the code object has no kernel " PGB_COMPILED_PROBE;
   if (why) {
     (void)hipGetLastError();
     (void)hipModuleUnload(mod);
@@ -74,6 +83,7 @@ extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64
   if (h->cl_module) (void)hipModuleUnload(h->cl_module);
   h->cl_module = mod;
   h->cl_fn = fn;
+  h->cl_probe = probe;
   if (h->cl_nparams != n_params) memset(&h->cl_prm, 0, sizeof h->cl_prm);
   h->cl_nparams = n_params;
   compiled_size_grid(h);
@@ -104,6 +114,26 @@ extern "C" int pgb_set_loglik_aux(pgb_handle* h, const double* aux_dev) {
     HIPCHK(hipStreamSynchronize(h->stream));
     return fail(PGB_E_INVALID, "the aux column has non-finite values");
   }
+  return PGB_OK;
+}
+
+extern "C" int pgb_compiled_probe(pgb_handle* h, const double* y, const double* mu, const double* aux, int64_t n,
+                                  double* out) {
+  if (!h) return fail(PGB_E_INVALID, "null handle");
+  JOIN_ASYNC(h);
+  if (h->s.family != PGB_FAMILY_COMPILED)
+    return fail(PGB_E_INVALID, "the sampler was not created with the compiled family");
+  if (!h->cl_probe) return fail(PGB_E_INVALID, "pgb_set_loglik_code first");
+  if (n < 0) return fail(PGB_E_INVALID, "n must be >= 0");
+  if (n == 0) return PGB_OK;
+  if (!y || !mu || !out) return fail(PGB_E_INVALID, "null argument");
+  long long nn = (long long)n;
+  pgb_compiled_params prm = h->cl_prm;
+  void* args[] = {(void*)&y, (void*)&mu, (void*)&aux, (void*)&nn, (void*)&prm, (void*)&out};
+  long long g = (nn + BT - 1) / BT;
+  if (g > 4096) g = 4096;  // (a grid-stride loop covers the rest)
+  HIPCHK(hipModuleLaunchKernel(h->cl_probe, (unsigned)g, 1, 1, BT, 1, 1, 0, h->stream, args, nullptr));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return PGB_OK;
 }
 

@@ -67,10 +67,11 @@ struct pgb_handle {
   // callback family: the host evaluates the per-row log-likelihood once per slot
   pgb_loglik_fn cb_fn;
   void* cb_ctx;
-  // compiled family (pgb_compiled_host.h): the loaded code object, its kernel, the params of the next launches
-  // (by value) and the aux column ([n_pad], zero unless pgb_set_loglik_aux set it)
+  // compiled family (pgb_compiled_host.h): the loaded code object, its kernel (and probe), the params of the next
+  // launches (by value) and the aux column ([n_pad], zero unless pgb_set_loglik_aux set it)
   hipModule_t cl_module;
   hipFunction_t cl_fn;
+  hipFunction_t cl_probe;
   int cl_nparams;
   pgb_compiled_params cl_prm;
   double* cl_aux;
@@ -162,6 +163,7 @@ extern "C" int32_t pgb_abi_version(void) { return PGB_ABI_VERSION; }
 // K = 2, 3, 4), per family for single-output constant leaves (one family's code per instance).
 typedef void (*ll_kernel_t)(const Dev*, int, int, const Cmd*, const Ctrl*, const Job*, const Acc*, const InitAcc*);
 static ll_kernel_t select_ll_kernel(int K, bool lin, int family) {
+  if (family == PGB_FAMILY_COMPILED) return nullptr;  // (a module kernel for any K: pgb_set_loglik_code)
   if (K > 1 && lin) return k_loglik<0, -1, true>;
   if (K > 1) {  // constant K-vector leaves: softmax (factorised evaluation, any K) or Normal mean / scale (K = 2)
     if (family != PGB_FAMILY_CATEGORICAL) return k_loglik<2, PGB_FAMILY_NORMAL_MEANSCALE, false>;
@@ -181,7 +183,6 @@ static ll_kernel_t select_ll_kernel(int K, bool lin, int family) {
     case PGB_FAMILY_ASYMLAPLACE: return k_loglik<1, PGB_FAMILY_ASYMLAPLACE, false>;
     case PGB_FAMILY_GAMMA_LOG: return k_loglik<1, PGB_FAMILY_GAMMA_LOG, false>;
     case PGB_FAMILY_CALLBACK: return k_loglik<1, PGB_FAMILY_CALLBACK, false>;
-    case PGB_FAMILY_COMPILED: return nullptr;  // (a module kernel: pgb_set_loglik_code)
     default: return k_loglik<1, PGB_FAMILY_STUDENT_T, false>;
   }
 }
@@ -201,16 +202,18 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
       return fail(PGB_E_INVALID, "CATEGORICAL needs 2 <= n_outputs <= " PGB_STR(PGB_MAX_OUTPUTS));
   } else if (s->family == PGB_FAMILY_NORMAL_MEANSCALE) {
     if (s->n_outputs != 2) return fail(PGB_E_INVALID, "NORMAL_MEANSCALE needs n_outputs == 2");
+  } else if (s->family == PGB_FAMILY_COMPILED) {  // a body of K = n_outputs predictors (k_loglik_compiled.hip)
+    if (s->n_outputs < 1 || s->n_outputs > PGB_MAX_OUTPUTS)
+      return fail(PGB_E_INVALID, "COMPILED needs 1 <= n_outputs <= " PGB_STR(PGB_MAX_OUTPUTS));
+    if (s->response != PGB_RESPONSE_CONSTANT) return fail(PGB_E_UNSUPPORTED, "the compiled family has constant leaves");
   } else if (s->family == PGB_FAMILY_NORMAL || s->family == PGB_FAMILY_BERNOULLI_PROBIT ||
              s->family == PGB_FAMILY_BERNOULLI_LOGIT || s->family == PGB_FAMILY_POISSON_LOG ||
              s->family == PGB_FAMILY_NEGBIN_LOG || s->family == PGB_FAMILY_ASYMLAPLACE ||
              s->family == PGB_FAMILY_STUDENT_T || s->family == PGB_FAMILY_GAMMA_LOG ||
-             s->family == PGB_FAMILY_CALLBACK || s->family == PGB_FAMILY_COMPILED) {
+             s->family == PGB_FAMILY_CALLBACK) {
     if (s->n_outputs != 1) return fail(PGB_E_INVALID, "this family has a single output");
     if (s->family == PGB_FAMILY_CALLBACK && s->response != PGB_RESPONSE_CONSTANT)
       return fail(PGB_E_UNSUPPORTED, "the callback family has constant leaves");
-    if (s->family == PGB_FAMILY_COMPILED && s->response != PGB_RESPONSE_CONSTANT)
-      return fail(PGB_E_UNSUPPORTED, "the compiled family has constant leaves");
   } else {
     return fail(PGB_E_UNSUPPORTED, "unknown family");
   }
@@ -250,6 +253,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   h->cb_ctx = nullptr;
   h->cl_module = nullptr;
   h->cl_fn = nullptr;
+  h->cl_probe = nullptr;
   h->cl_nparams = -1;
   memset(&h->cl_prm, 0, sizeof h->cl_prm);
   h->cl_aux = nullptr;

@@ -185,6 +185,11 @@ class PySampler:
         # build as family "callback" (set_compiled_likelihood) -- the same per-row values, the same sampler
         self._compiled_on_host = settings.family == "compiled" and lib.backend_name != "hip-gfx950"
         if self._compiled_on_host:
+            if settings.n_outputs != 1:
+                raise _abi.PGBError(
+                    f"the compiled family with n_outputs = {settings.n_outputs} runs on the HIP backend only: a CPU "
+                    f"backend ({lib.backend_name}) runs a compiled body as its callback family, which has a single "
+                    "output")
             cs.family = _abi.FAMILIES["callback"]
         # (device backends: a stream object to keep alive; the CPU oracle has none)
         self._stream = mem.sampler_stream() if hasattr(mem, "sampler_stream") else None
@@ -304,6 +309,10 @@ class PySampler:
         n = self.settings.n
         if lik.aux is not None and lik.aux.size != n:
             raise ValueError(f"aux must hold n = {n} values, got {lik.aux.size}")
+        K = int(getattr(lik, "n_outputs", 1))
+        if K != self.settings.n_outputs:
+            raise _abi.PGBError(f"the compiled likelihood has {K} outputs, the sampler n_outputs = "
+                                f"{self.settings.n_outputs}")
         if not self._compiled_on_host:
             build = lik.compiled(lib.max_particles)
             set_code, set_aux = lib.compiled_entry_points()
@@ -324,6 +333,30 @@ class PySampler:
         self._cl_nparams = build.n_params
         self._cl_build = build
         self._lik_key = None
+
+    def compiled_probe(self, y, mu, aux=None) -> np.ndarray:
+        """The loaded code object's body on given rows, evaluated on the device (``pgb_compiled_probe``): ``mu`` is
+        [K][n] (or [n] for one output); the params are those of the last :meth:`set_likelihood`.  The values are
+        clamped like the sampler takes them."""
+        if self._compiled_on_host or getattr(self, "_cl_code", None) is None:
+            raise _abi.PGBError("compiled_probe needs the HIP backend and set_compiled_likelihood first")
+        lib, mem = self.backend.lib, self.backend.mem
+        y = np.ascontiguousarray(y, np.float64).ravel()
+        n = y.size
+        K = self.settings.n_outputs
+        mu = np.ascontiguousarray(mu, np.float64).reshape(K, n)
+        yd, md = mem.from_host(y), mem.from_host(mu)
+        ad = None
+        if aux is not None:
+            a = np.ascontiguousarray(aux, np.float64).ravel()
+            if a.size != n:
+                raise ValueError(f"aux must hold n = {n} values, got {a.size}")
+            ad = mem.from_host(a)
+        od = mem.empty((max(n, 1),), np.float64)
+        probe = lib.compiled_probe_entry_point()
+        lib.check(probe(self._h, mem.ptr(yd), mem.ptr(md), None if ad is None else mem.ptr(ad), n, mem.ptr(od)),
+                  "pgb_compiled_probe")
+        return np.asarray(mem.to_host(od), np.float64).ravel()[:n].copy()
 
     # -- one astep -----------------------------------------------------------------
     def step(self, tune: bool, fetch: bool = True):

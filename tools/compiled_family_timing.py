@@ -8,10 +8,16 @@ asteps, each ended by a device synchronise:
 * ``compiled``  the same check loss written as a body (CompiledLikelihood), its run-time code object,
 * ``callback``  the same body as a Python callback (family "callback"), at n = 10 k: too slow at full size.
 
-Also reports the compiled kernel's resource usage and compile time (on a fresh cache), and whether the two full-size
-runs' sum_trees are bit-identical.  Prints ONE JSON line.
+Two K-vector legs, the same protocol (a body of n_outputs = K runs in the library's K-vector pass):
 
-  python tools/compiled_family_timing.py [--steps 20] [--tune 10] [--compiled-only]
+* ``meanscale`` Normal mean / scale (K = 2) as a body against the built-in ``normal_meanscale`` at cfg2 size,
+* ``softmax``   the softmax (K = 4) as a body -- unfactorised: the body sees mu, not the row / leaf parts -- against
+  the built-in (factorised) ``categorical`` at cfg5 size.
+
+Also reports the compiled kernels' resource usage and compile time (on a fresh cache), and whether the compared
+full-size runs' sum_trees are bit-identical.  Prints ONE JSON line.
+
+  python tools/compiled_family_timing.py [--steps 20] [--tune 10] [--compiled-only] [--kvector-only]
 """
 
 from __future__ import annotations
@@ -29,6 +35,24 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 CHECK_LOSS = "double u = (y - mu) / b;  return -(u * (u < 0.0 ? q - 1.0 : q));"
+# pgb_loglik_meanscale_t / pgb_loglik_cat_t as bodies (tests/test_compiled_kvector.py)
+MEANSCALE = """double sd = mu[1] < 0.0 ? -mu[1] : mu[1];
+if (!(sd >= 1e-8)) sd = 1e-8;
+if (sd > 1.0e300) sd = 1.0e300;
+double z = (y - mu[0]) / sd;
+return -log(sd) - 0.5 * (z * z);"""
+SOFTMAX = """double mx = mu[0];
+for (int k = 1; k < K; ++k) if (mu[k] > mx) mx = mu[k];
+double sum = 0.0;
+for (int k = 0; k < K; ++k) sum += exp(mu[k] - mx);
+int c = (int)y;
+if (c < 0) c = 0;
+if (c > K - 1) c = K - 1;
+double muc = mu[0];
+for (int k = 1; k < K; ++k) if (k == c) muc = mu[k];
+double ll = (muc - mx) - log(sum);
+if (!(sum >= 1.0)) ll = -2047.0;
+return ll > 0.0 ? 0.0 : ll;"""
 
 
 def data(n, p=50, seed=3415):
@@ -38,15 +62,15 @@ def data(n, p=50, seed=3415):
     return X, f + rng.normal(0, 1.0 + X[:, 0], n)
 
 
-def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40):
+def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40, K=1, params=(0.25, 0.9)):
     import torch
 
     from pymc_bart_amd.sampler import PyBartSettings, PySampler, default_backend
 
-    st = PyBartSettings.from_data(X, Y, m=m, num_particles=P, seed=7, family=family)
+    st = PyBartSettings.from_data(X, Y, m=m, num_particles=P, seed=7, family=family, n_outputs=K)
     p = X.shape[1]
     s = PySampler(st, X, Y, np.zeros(p, np.int32), np.ones(p), backend=default_backend())
-    params = [0.25, 0.9]
+    params = list(params)
     if lik is not None:
         s.set_compiled_likelihood(lik)
     if callback is not None:
@@ -67,13 +91,44 @@ def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40):
     return float(np.median(ms)), float(np.mean(ms)), st_host
 
 
+def kvector_legs(tune, steps) -> dict:
+    """The two K-vector legs: compiled against built-in, ms per astep (median) and bit-identity of sum_trees."""
+    from pymc_bart_amd.compiled import CompiledLikelihood
+    from pymc_bart_amd.workloads import cfg5
+
+    out = {}
+    X, Y = data(100_000)
+    lik = CompiledLikelihood(MEANSCALE, n_outputs=2)
+    b_med, _, b_st = run(X, Y, "normal_meanscale", tune, steps, K=2, params=())
+    c_med, _, c_st = run(X, Y, "compiled", tune, steps, lik=lik, K=2, params=())
+    out["meanscale_k2"] = {"config": "cfg2 size (n=100000 p=50 m=200 P=40)", "builtin_ms": round(b_med, 3),
+                           "compiled_ms": round(c_med, 3), "compiled_over_builtin": round(c_med / b_med, 3),
+                           "sum_trees_bit_identical": bool(np.array_equal(b_st, c_st)),
+                           "kernel": lik.compiled(64).resources}
+    w = cfg5()
+    lik = CompiledLikelihood(SOFTMAX, n_outputs=4)
+    kw = dict(K=4, params=(), m=w["m"], P=w["num_particles"])
+    b_med, _, b_st = run(w["X"], w["Y"], "categorical", tune, steps, **kw)
+    c_med, _, c_st = run(w["X"], w["Y"], "compiled", tune, steps, lik=lik, **kw)
+    out["softmax_k4"] = {"config": w["name"], "builtin_factorised_ms": round(b_med, 3), "compiled_ms": round(c_med, 3),
+                         "compiled_over_builtin": round(c_med / b_med, 3),
+                         "sum_trees_bit_identical": bool(np.array_equal(b_st, c_st)),
+                         "kernel": lik.compiled(64).resources}
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--tune", type=int, default=10)
     ap.add_argument("--compiled-only", action="store_true", help="only the full-size compiled run (under a profiler)")
+    ap.add_argument("--kvector-only", action="store_true", help="only the two K-vector legs")
     args = ap.parse_args(argv)
     os.environ.setdefault("PGB_JIT_CACHE", tempfile.mkdtemp(prefix="pgb_jit_timing_"))  # (a fresh cache: a real compile)
+    if args.kvector_only:
+        print(json.dumps({"metric": "ms_per_astep", "tune": args.tune, "steps": args.steps,
+                          **kvector_legs(args.tune, args.steps)}))
+        return 0
     from pymc_bart_amd.compiled import CompiledLikelihood
 
     t0 = time.perf_counter()
@@ -107,6 +162,7 @@ def main(argv=None) -> int:
         "compile_seconds": round(compile_s, 2), "kernel": build.resources,
         "means_ms": {"builtin": round(b_mean, 3), "compiled": round(c_mean, 3), "n10k_callback": round(cb_mean, 3),
                      "n10k_compiled": round(cs_mean, 3)},
+        **kvector_legs(args.tune, args.steps),
     }
     print(json.dumps(line))
     return 0

@@ -2,10 +2,13 @@
  * pgbart_compiled.h -- the "compiled" likelihood family: a per-row log-density written by the user as a
  * short C function body, compiled at run time into a k_loglik instance for gfx950 (a code object the HIP
  * library loads) and, for the CPU backends, into a host function with the pgb_loglik_fn signature.
- * A body may also take K = 2 .. PGB_MAX_OUTPUTS linear predictors (a sampler with n_outputs = K, constant
- * leaves): the code object is then the library's K-vector pass, k_loglik<K> (K <= 4) or k_loglik<0> (run-time
- * K), with the body at its evaluation sites.  No CPU backend runs a K-vector body (the callback family has one
- * output): its host build serves as a reference evaluator only.
+ * A body may also take K = 2 .. PGB_MAX_OUTPUTS linear predictors (a sampler with n_outputs = K): the code
+ * object is then the library's K-vector pass, k_loglik<K> (K <= 4) or k_loglik<0> (run-time K), with the body
+ * at its evaluation sites.  A code object holds ONE pass kernel, for constant leaves or for linear leaves
+ * (response linear / mix: k_loglik<1, ., true>, or the run-time-K linear path with K fixed at compile time);
+ * its layout record says which, and the library takes the one that matches the sampler's response.  No CPU
+ * backend runs a K-vector body or linear leaves (the callback family has one output and constant leaves): the
+ * host build of such a body serves as a reference evaluator only.
  *
  * Kept apart from pgbart.h on purpose: pgbart.h is the ABI every backend (the CPU oracle included) exports in
  * full; the entry points below exist in the HIP library only.  A CPU backend runs the same body as family
@@ -33,7 +36,7 @@
 
 /* The layout record every compiled code object carries (a __device__ global named PGB_COMPILED_LAYOUT): the
  * library compares it with its own values before the first launch and refuses a code object built for the
- * other particle build or from other kernel headers. */
+ * other particle build, from other kernel headers, for another number of outputs or for the other kind of leaves. */
 typedef struct {
   int32_t magic;          /* PGB_COMPILED_MAGIC */
   int32_t max_particles;  /* PGB_MAX_PARTICLES */
@@ -41,6 +44,8 @@ typedef struct {
   int32_t n_outputs;      /* the K of the body's mu (1: a scalar mu) */
   int64_t sizeof_dev, sizeof_job, sizeof_cmd, sizeof_ctrl, sizeof_acc;
   uint64_t headers_hash;  /* PGB_HEADERS_HASH: a hash of the kernel headers (pymc_bart_amd/compiled.py) */
+  int32_t linear_leaves;  /* 0: the constant-leaf pass, 1: the linear-leaf pass (response linear / mix) */
+  int32_t reserved_;      /* 0 */
 } pgb_compiled_layout;
 
 /* The params of one launch, by value (they arrive in SGPRs with the kernel arguments). */
@@ -55,7 +60,8 @@ extern "C" {
 #endif
 /* Load a compiled code object (hipModuleLoadData) for a sampler created with family PGB_FAMILY_COMPILED and
  * check its layout record.  PGB_E_INVALID for another family, bytes that are not a gfx950 code object, a code
- * object without the kernel or the record, or a record that does not match this library; the handle stays usable
+ * object without the kernel or the record, or a record that does not match this library or the sampler
+ * (outputs; constant against linear / mix leaves); the handle stays usable
  * (a refused image is never launched).  A new code object replaces the old one; pgb_destroy unloads it.
  * n_params: the params the body declares (pgb_set_likelihood then takes exactly that many). */
 int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64_t bytes, int32_t n_params);

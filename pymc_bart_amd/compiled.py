@@ -13,7 +13,9 @@ Both sides evaluate the body with the same vocabulary (table-driven ``exp`` / ``
 ``softplus`` / ``lgamma`` on the tables of ``include/pgbart_spec.h``, explicit comparisons), so that a CPU backend
 checks the GPU chain bit for bit.  A body of ``n_outputs = K >= 2`` reads ``mu[0] .. mu[K-1]``: its code object is the
 library's K-vector pass; no CPU backend runs it (the callback family has one output), and its host build is an
-evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is held to.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
+evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is held to.  With ``linear=True`` the
+code object holds the library's linear-leaf pass instead (``response="linear"`` / ``"mix"``, one output or K): one pass
+kernel per code object, and HIP only -- the CPU backends' callback family has constant leaves.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
 everything that goes into them.
 """
 
@@ -223,10 +225,10 @@ def cache_dir() -> str:
     return os.environ.get("PGB_JIT_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "pymc_bart_amd", "jit")
 
 
-def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1) -> str:
+def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1, linear: bool = False) -> str:
     h = hashlib.sha256()
     h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
-                         "n_outputs": int(n_outputs),
+                         "n_outputs": int(n_outputs), "linear": bool(linear),
                          "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
                          "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
                         sort_keys=True).encode())
@@ -247,10 +249,11 @@ def _write_atomic(path: str, data: bytes) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------- the builds
-def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1) -> str:
+def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1, linear: bool = False) -> str:
     return "\n".join([
         f"#define PGB_COMPILED_NPARAMS {len(names)}",
         f"#define PGB_COMPILED_NOUT {int(n_outputs)}",
+        f"#define PGB_COMPILED_LINEAR {1 if linear else 0}",
         f"#define PGB_COMPILED_EXPLOG {1 if explog else 0}",
         f"#define PGB_HEADERS_HASH {headers_hash()}ull",
         "#define PGB_COMPILED_PARAMS " + "".join(f", const double {nm}" for nm in names),
@@ -373,12 +376,15 @@ def kernel_resources(code_object_path: str) -> dict:
 
 class CompiledLoglik:
     """One build of a body: the code object (``code``), the host library (``host_lib``), the kernel's resource
-    usage (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit."""
+    usage (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit.  ``linear``: the code
+    object's pass kernel is the linear-leaf pass (a sampler with ``response="linear"`` / ``"mix"`` takes it, one with
+    constant leaves refuses it, and the other way round)."""
 
     def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached,
-                 n_outputs=1):
+                 n_outputs=1, linear=False):
         self.key, self.body, self.param_names, self.max_particles = key, body, tuple(param_names), int(max_particles)
         self.n_outputs = int(n_outputs)
+        self.linear = bool(linear)
         self.code, self.host_lib, self.resources = code, host_lib, resources
         self.compile_seconds, self.cached = compile_seconds, cached
         self._host = None
@@ -435,20 +441,24 @@ class CompiledContext(C.Structure):
 
 
 def _warn_scratch(b: "CompiledLoglik") -> None:
-    if b.n_outputs > 1 and b.resources.get("scratch_bytes", 0) > 0:
-        warnings.warn(f"the likelihood body of {b.n_outputs} outputs puts {b.resources['scratch_bytes']} B per thread "
+    if (b.n_outputs > 1 or b.linear) and b.resources.get("scratch_bytes", 0) > 0:
+        warnings.warn(f"the likelihood body of {b.n_outputs} outputs{' (linear leaves)' if b.linear else ''} puts "
+                      f"{b.resources['scratch_bytes']} B per thread "
                       "in scratch memory: mu lives in registers, and a run-time index such as mu[(int)y] moves it "
                       "out.  Pick by comparison instead -- for (int k = 0; k < K; ++k) if (k == c) m = mu[k]; -- "
                       "which is what the built-in softmax does", RuntimeWarning, stacklevel=3)
 
 
-def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1) -> CompiledLoglik:
+def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1,
+                   linear: bool = False) -> CompiledLoglik:
     """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
-    (64 or 128) and ``n_outputs`` predictors -- or take it from the cache."""
+    (64 or 128) and ``n_outputs`` predictors -- or take it from the cache.  ``linear``: the code object's pass is
+    the linear-leaf one (``response="linear"`` / ``"mix"``) instead of the constant-leaf one."""
     K = check_outputs(n_outputs)
     names = validate(body, param_names, K)
     mp = 128 if int(max_particles) > 64 else 64
-    key = cache_key(body, names, mp, K)
+    linear = bool(linear)
+    key = cache_key(body, names, mp, K, linear)
     root = cache_dir()
     os.makedirs(root, exist_ok=True)
     co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
@@ -457,7 +467,7 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
             meta = json.load(fh)
         with open(co_path, "rb") as fh:
             code = fh.read()
-        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K)
+        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K, linear)
         _warn_scratch(b)
         return b
     t0 = time.perf_counter()
@@ -472,7 +482,7 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
         if r.returncode != 0:
             raise _compile_error(r.stderr, body, "host")
         with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
-            fh.write(_body_defs(names, mp, uses_tables(body), K))
+            fh.write(_body_defs(names, mp, uses_tables(body), K, linear))
         with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
             fh.write(_body_text(body))
         co_tmp = os.path.join(tmp, "k.co")
@@ -489,10 +499,10 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
             host = fh.read()
     _write_atomic(co_path, code)
     _write_atomic(so_path, host)
-    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "resources": resources,
+    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "linear": linear, "resources": resources,
             "compile_seconds": seconds}
     _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
-    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K)
+    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K, linear)
     _warn_scratch(b)
     return b
 
@@ -519,6 +529,12 @@ class CompiledLikelihood:
     The value is clamped to [-2047, 2047] (NaN -> -2047) and summed in fixed point exactly like family
     ``"callback"``; on the GPU the evaluation runs inside the sampler's own likelihood kernel.
 
+    Leaves: any ``response`` of the ``BARTOp`` -- ``"constant"``, ``"linear"``, ``"mix"`` -- with one output or K, like
+    the built-in families.  ``mu`` then includes the leaf's slope term; the body does not know about leaves.  The
+    linear-leaf pass is a code object of its own (``compiled(max_particles, linear=True)``), built when a sampler
+    with such a response first asks for it.  Linear / mix leaves of a compiled likelihood run on the HIP backend
+    only (a CPU backend runs the body as its callback family, which has constant leaves).
+
     >>> CompiledLikelihood("double u = (y - mu) / b;  return -(u * (u < 0.0 ? q - 1.0 : q));",
     ...                    params={"b": 0.25, "q": "q_var"})            # doctest: +SKIP
     """
@@ -536,11 +552,12 @@ class CompiledLikelihood:
         self._builds = {}
         self.compiled(64)  # (errors surface here, not at the first step)
 
-    def compiled(self, max_particles: int = 64) -> CompiledLoglik:
+    def compiled(self, max_particles: int = 64, linear: bool = False) -> CompiledLoglik:
         mp = 128 if int(max_particles) > 64 else 64
-        if mp not in self._builds:
-            self._builds[mp] = compile_loglik(self.body, self.param_names, mp, self.n_outputs)
-        return self._builds[mp]
+        k = (mp, bool(linear))
+        if k not in self._builds:
+            self._builds[k] = compile_loglik(self.body, self.param_names, mp, self.n_outputs, bool(linear))
+        return self._builds[k]
 
     def params(self, point=None):
         from .pgbart import _from_point

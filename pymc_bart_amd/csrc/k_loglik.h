@@ -179,12 +179,16 @@ __device__ __forceinline__ long long quant_ll(double ll, double cl) {
 // pgb_compiled_eval(y, mu, aux, params, tables) in front of it.  There k_loglik is the __forceinline__ body of the
 // kernel k_loglik_compiled, with two arguments more: the aux column ([n_pad], like y) and the params (by value).
 // A body of K >= 2 outputs (PGB_COMPILED_NOUT) takes mu as the K-array of the K-vector sites (PGB_CL_LLK); the
-// one-output sites are then never instantiated, and vice versa.
+// one-output sites are then never instantiated, and vice versa.  With linear leaves (LIN) a one-output body sits
+// in the plain path behind pgb_leaf_pred; a K-output body in the run-time-K path, where the K predictors of a row
+// -- (row part [+ offset]) + pgb_leaf_pred, the built-in order -- are materialised into an array of PGB_CL_NOUT
+// doubles (K is a compile-time constant of a code object: unrolled, in registers).
 #ifdef PGB_COMPILED_LOGLIK
 #define PGB_LL_ENTRY(WGS) __device__ __forceinline__
 #define PGB_LL_EXTRA_ARGS , const double* __restrict__ cl_aux, const pgb_compiled_params cl_prm
 #define PGB_CL_AUX(row) cl_aux[row]
 #define PGB_CL_AUXP cl_aux
+#define PGB_CL_NOUT PGB_COMPILED_NOUT
 #if PGB_COMPILED_NOUT == 1
 #define PGB_CL_LL(y, mu, aux) pgb_compiled_eval((y), (mu), (aux), cl_prm, &tb)
 #define PGB_CL_LLK(y, mu, aux) 0.0
@@ -197,6 +201,7 @@ __device__ __forceinline__ long long quant_ll(double ll, double cl) {
 #define PGB_LL_EXTRA_ARGS
 #define PGB_CL_AUX(row) 0.0
 #define PGB_CL_AUXP nullptr
+#define PGB_CL_NOUT 1
 #define PGB_CL_LL(y, mu, aux) 0.0
 #define PGB_CL_LLK(y, mu, aux) 0.0
 #endif
@@ -1033,7 +1038,15 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
               const double nk = k == 0 ? nv[e] : noi[(size_t)k * S.n_pad + base + e];
               return (S.has_off ? nk + goff[(size_t)k * S.n_pad + base + e] : nk) + vk;
             };
-            const double llv = loglik_fn(S.family, K, yv[e], mu, &tb);
+            double llv;
+            if constexpr (CMPLK) {  // (the body reads an array: the code object's K, unrolled)
+              double mv[PGB_CL_NOUT];
+#pragma unroll
+              for (int k = 0; k < PGB_CL_NOUT; ++k) mv[k] = mu(k);
+              llv = PGB_CL_LLK(yv[e], mv, PGB_CL_AUX(base + e));
+            } else {
+              llv = loglik_fn(S.family, K, yv[e], mu, &tb);
+            }
             const long long q = quant_ll(llv, cl);
             if (side == 0) v0 += q; else if (side == 1) v1 += q; else v2 += q;
           }
@@ -1266,7 +1279,17 @@ void k_loglik(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restric
             auto mu_cur = [&](int k) {
               return (k == 0 ? S.pack[row].x : S.packx[(size_t)(k > 0 ? k - 1 : 0) * S.n_pad + row]) + offk(k);
             };
-            if constexpr (LIN && KT == 0) {  // (the rare instance keeps the predictors as functions, see loglik_fn)
+            if constexpr (LIN && KT == 0 && CMPLK) {  // (compiled family, linear leaves: the code object's K)
+              double ms[PGB_CL_NOUT], mc[PGB_CL_NOUT];
+#pragma unroll
+              for (int k = 0; k < PGB_CL_NOUT; ++k) {
+                ms[k] = mu_stump(k);
+                mc[k] = mu_cur(k);
+              }
+              const double ax = PGB_CL_AUX(row);
+              ce[0] += quant_ll(PGB_CL_LLK(yr, ms, ax), S.sc.cl);
+              ce[1] += quant_ll(PGB_CL_LLK(yr, mc, ax), S.sc.cl);
+            } else if constexpr (LIN && KT == 0) {  // (the rare instance keeps the predictors as functions, see loglik_fn)
               ce[0] += quant_ll(loglik_fn(S.family, Kn, yr, mu_stump, &tb), S.sc.cl);
               ce[1] += quant_ll(loglik_fn(S.family, Kn, yr, mu_cur, &tb), S.sc.cl);
             } else {

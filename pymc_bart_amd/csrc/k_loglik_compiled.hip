@@ -5,12 +5,16 @@
 // build directory:
 //   pgb_compiled_body.inc       PGB_COMPILED_PARAMS (", const double <name>" per param), PGB_COMPILED_ARGS(P)
 //                               (", (P).v[i]" per param), PGB_COMPILED_NPARAMS, PGB_COMPILED_NOUT (K),
-//                               PGB_COMPILED_EXPLOG, PGB_HEADERS_HASH
+//                               PGB_COMPILED_LINEAR (0: constant leaves, 1: linear leaves), PGB_COMPILED_EXPLOG,
+//                               PGB_HEADERS_HASH
 //   pgb_compiled_body_text.inc  the user's body, behind a #line directive (compiler messages quote the user's lines)
 // The kernel is the library's constant-leaf pass with the generated function at every place where the family is
 // evaluated: k_loglik<1, PGB_FAMILY_COMPILED, false> (plain, not dense, path) for one output; for K outputs the
 // K-vector pass of the same K as the built-in families -- k_loglik<K> for K = 2, 3, 4 (loops unrolled), k_loglik<0>
-// (run-time K) above -- at the built-in instance's occupancy.  Next to it: the layout record the library checks
+// (run-time K) above -- at the built-in instance's occupancy.  With PGB_COMPILED_LINEAR the ONE pass kernel of the
+// code object is the linear-leaf pass instead (response linear / mix): k_loglik<1, PGB_FAMILY_COMPILED, true> for one
+// output, k_loglik<0, PGB_FAMILY_COMPILED, true> -- the run-time-K linear path with the K predictors of a row in an
+// array of K doubles -- for K outputs, at the launch bounds of the built-in linear instances.  Next to it: the layout record the library checks
 // before the first launch (pgb_set_loglik_code), and a probe kernel that evaluates the body on given rows
 // (pgb_compiled_probe).
 #include <hip/hip_runtime.h>
@@ -31,6 +35,13 @@
 #endif
 #if PGB_COMPILED_NOUT < 1 || PGB_COMPILED_NOUT > PGB_MAX_OUTPUTS
 #error "PGB_COMPILED_NOUT must be in [1, PGB_MAX_OUTPUTS]"
+#endif
+
+#ifndef PGB_COMPILED_LINEAR
+#define PGB_COMPILED_LINEAR 0
+#endif
+#if PGB_COMPILED_LINEAR != 0 && PGB_COMPILED_LINEAR != 1
+#error "PGB_COMPILED_LINEAR must be 0 or 1"
 #endif
 
 #define PGB_COMPILED_LOGLIK 1
@@ -74,6 +85,9 @@ __device__ __forceinline__ double pgb_compiled_eval(double y, pgb_compiled_mu mu
 #if PGB_COMPILED_NOUT == 1
 #define PGB_CL_KT 1
 #define PGB_CL_WGS 3
+#elif PGB_COMPILED_LINEAR  // (K-vector linear leaves: the run-time-K path for any K, as k_loglik<0, -1, true>)
+#define PGB_CL_KT 0
+#define PGB_CL_WGS 2
 #elif PGB_COMPILED_NOUT <= 4
 #define PGB_CL_KT PGB_COMPILED_NOUT
 #define PGB_CL_WGS PGB_LLK_WGS
@@ -86,7 +100,7 @@ extern "C" __global__ __launch_bounds__(BT, PGB_CL_WGS)
 void k_loglik_compiled(const Dev* __restrict__ Sp, int par, int nwg, const Cmd* __restrict__ cmds,
                        const Ctrl* __restrict__ ctrls, const Job* __restrict__ jobs_all, const Acc* __restrict__ acc_all,
                        const InitAcc* __restrict__ ias, const double* __restrict__ aux, const pgb_compiled_params prm) {
-  k_loglik<PGB_CL_KT, PGB_FAMILY_COMPILED, false>(Sp, par, nwg, cmds, ctrls, jobs_all, acc_all, ias, aux, prm);
+  k_loglik<PGB_CL_KT, PGB_FAMILY_COMPILED, PGB_COMPILED_LINEAR != 0>(Sp, par, nwg, cmds, ctrls, jobs_all, acc_all, ias, aux, prm);
 }
 
 // pgb_compiled_probe: out[i] = the clamped body at (y[i], mu[0..K-1][i], aux[i] or 0.0, prm), i < n; the tables
@@ -115,4 +129,4 @@ void k_loglik_compiled_probe(const double* __restrict__ y, const double* __restr
 extern "C" __device__ pgb_compiled_layout pgb_compiled_layout_record = {
     PGB_COMPILED_MAGIC, PGB_MAX_PARTICLES, PGB_COMPILED_NPARAMS, PGB_COMPILED_NOUT,
     (int64_t)sizeof(Dev), (int64_t)sizeof(Job), (int64_t)sizeof(Cmd), (int64_t)sizeof(Ctrl), (int64_t)sizeof(Acc),
-    (uint64_t)PGB_HEADERS_HASH};
+    (uint64_t)PGB_HEADERS_HASH, PGB_COMPILED_LINEAR, 0};

@@ -11,7 +11,8 @@ static void compiled_size_grid(pgb_handle* h) {
   int per_cu = 0, cus = 0;
   if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->cl_fn, BT, 0) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0) {
-    if (h->d.K >= 2 && h->d.K <= 4 && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;  // (as the built-in K = 2, 3, 4)
+    // (as the built-in K = 2, 3, 4 with constant leaves; the linear pass is the run-time-K path: what stays resident)
+    if (h->d.K >= 2 && h->d.K <= 4 && h->d.response == PGB_RESPONSE_CONSTANT && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;
     long long g = (long long)per_cu * cus;
     if (g < 256) g = 256;
     if (g > 2048) g = 2048;
@@ -66,6 +67,13 @@ extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64
   else if (rec.n_outputs != h->s.n_outputs) {
     snprintf(why_k, sizeof why_k, "the code object was compiled for %d outputs, the sampler has n_outputs = %d",
              (int)rec.n_outputs, (int)h->s.n_outputs);
+    why = why_k;
+  } else if ((rec.linear_leaves != 0) != (h->s.response != PGB_RESPONSE_CONSTANT) ||
+             (rec.linear_leaves != 0 && rec.linear_leaves != 1)) {
+    const char* resp = h->s.response == PGB_RESPONSE_CONSTANT ? "constant"
+                       : h->s.response == PGB_RESPONSE_LINEAR ? "linear" : "mix";
+    snprintf(why_k, sizeof why_k, "the code object was compiled for %s leaves, the sampler has response = %s",
+             rec.linear_leaves == 0 ? "constant" : rec.linear_leaves == 1 ? "linear" : "unknown", resp);
     why = why_k;
   }
   hipFunction_t fn = nullptr, probe = nullptr;

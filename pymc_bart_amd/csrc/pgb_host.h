@@ -205,7 +205,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   } else if (s->family == PGB_FAMILY_COMPILED) {  // a body of K = n_outputs predictors (k_loglik_compiled.hip)
     if (s->n_outputs < 1 || s->n_outputs > PGB_MAX_OUTPUTS)
       return fail(PGB_E_INVALID, "COMPILED needs 1 <= n_outputs <= " PGB_STR(PGB_MAX_OUTPUTS));
-    if (s->response != PGB_RESPONSE_CONSTANT) return fail(PGB_E_UNSUPPORTED, "the compiled family has constant leaves");
+    // (any response: the code object is the constant or the linear pass, pgb_set_loglik_code checks which)
   } else if (s->family == PGB_FAMILY_NORMAL || s->family == PGB_FAMILY_BERNOULLI_PROBIT ||
              s->family == PGB_FAMILY_BERNOULLI_LOGIT || s->family == PGB_FAMILY_POISSON_LOG ||
              s->family == PGB_FAMILY_NEGBIN_LOG || s->family == PGB_FAMILY_ASYMLAPLACE ||

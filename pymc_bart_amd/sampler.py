@@ -190,6 +190,11 @@ class PySampler:
                     f"the compiled family with n_outputs = {settings.n_outputs} runs on the HIP backend only: a CPU "
                     f"backend ({lib.backend_name}) runs a compiled body as its callback family, which has a single "
                     "output")
+            if settings.response != "constant":
+                raise _abi.PGBError(
+                    f"compiled likelihoods with linear / mix leaves (response = {settings.response!r}) run on the HIP "
+                    f"backend only: a CPU backend ({lib.backend_name}) runs a compiled body as its callback family, "
+                    "which has constant leaves")
             cs.family = _abi.FAMILIES["callback"]
         # (device backends: a stream object to keep alive; the CPU oracle has none)
         self._stream = mem.sampler_stream() if hasattr(mem, "sampler_stream") else None
@@ -314,7 +319,8 @@ class PySampler:
             raise _abi.PGBError(f"the compiled likelihood has {K} outputs, the sampler n_outputs = "
                                 f"{self.settings.n_outputs}")
         if not self._compiled_on_host:
-            build = lik.compiled(lib.max_particles)
+            # (one pass kernel per code object: the linear-leaf pass for response linear / mix)
+            build = lik.compiled(lib.max_particles, linear=self.settings.response != "constant")
             set_code, set_aux = lib.compiled_entry_points()
             self._cl_code = C.create_string_buffer(build.code, len(build.code))
             lib.check(set_code(self._h, C.cast(self._cl_code, C.c_void_p), len(build.code), build.n_params),

@@ -14,10 +14,16 @@ Two K-vector legs, the same protocol (a body of n_outputs = K runs in the librar
 * ``softmax``   the softmax (K = 4) as a body -- unfactorised: the body sees mu, not the row / leaf parts -- against
   the built-in (factorised) ``categorical`` at cfg5 size.
 
+Two linear-leaf legs (``--linear-only``), the same protocol: the code object's pass is then the linear-leaf one,
+
+* ``check_loss_linear``  the check loss with ``response="linear"`` against the built-in AsymmetricLaplace with linear
+  leaves (k_loglik<1, -1, true>: the family read at run time) at cfg2 size,
+* ``meanscale_k2_mix``   Normal mean / scale (K = 2) with ``response="mix"`` against the built-in (k_loglik<0, -1, true>).
+
 Also reports the compiled kernels' resource usage and compile time (on a fresh cache), and whether the compared
 full-size runs' sum_trees are bit-identical.  Prints ONE JSON line.
 
-  python tools/compiled_family_timing.py [--steps 20] [--tune 10] [--compiled-only] [--kvector-only]
+  python tools/compiled_family_timing.py [--steps 20] [--tune 10] [--compiled-only] [--kvector-only] [--linear-only]
 """
 
 from __future__ import annotations
@@ -62,12 +68,12 @@ def data(n, p=50, seed=3415):
     return X, f + rng.normal(0, 1.0 + X[:, 0], n)
 
 
-def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40, K=1, params=(0.25, 0.9)):
+def run(X, Y, family, tune, steps, lik=None, callback=None, m=200, P=40, K=1, params=(0.25, 0.9), response="constant"):
     import torch
 
     from pymc_bart_amd.sampler import PyBartSettings, PySampler, default_backend
 
-    st = PyBartSettings.from_data(X, Y, m=m, num_particles=P, seed=7, family=family, n_outputs=K)
+    st = PyBartSettings.from_data(X, Y, m=m, num_particles=P, seed=7, family=family, n_outputs=K, response=response)
     p = X.shape[1]
     s = PySampler(st, X, Y, np.zeros(p, np.int32), np.ones(p), backend=default_backend())
     params = list(params)
@@ -117,17 +123,47 @@ def kvector_legs(tune, steps) -> dict:
     return out
 
 
+def linear_legs(tune, steps) -> dict:
+    """The two linear-leaf legs: compiled against built-in, ms per astep (median) and bit-identity of sum_trees."""
+    from pymc_bart_amd.compiled import CompiledLikelihood
+
+    out = {}
+    X, Y = data(100_000)
+    lik = CompiledLikelihood(CHECK_LOSS, params={"b": 0.25, "q": 0.9})
+    b_med, _, b_st = run(X, Y, "asymmetric_laplace", tune, steps, response="linear")
+    c_med, _, c_st = run(X, Y, "compiled", tune, steps, lik=lik, response="linear")
+    out["check_loss_linear"] = {"config": "cfg2 size (n=100000 p=50 m=200 P=40), response linear",
+                                "builtin_ms": round(b_med, 3), "compiled_ms": round(c_med, 3),
+                                "compiled_over_builtin": round(c_med / b_med, 3),
+                                "sum_trees_bit_identical": bool(np.array_equal(b_st, c_st)),
+                                "kernel": lik.compiled(64, linear=True).resources}
+    lik = CompiledLikelihood(MEANSCALE, n_outputs=2)
+    b_med, _, b_st = run(X, Y, "normal_meanscale", tune, steps, K=2, params=(), response="mix")
+    c_med, _, c_st = run(X, Y, "compiled", tune, steps, lik=lik, K=2, params=(), response="mix")
+    out["meanscale_k2_mix"] = {"config": "cfg2 size (n=100000 p=50 m=200 P=40), response mix",
+                               "builtin_ms": round(b_med, 3), "compiled_ms": round(c_med, 3),
+                               "compiled_over_builtin": round(c_med / b_med, 3),
+                               "sum_trees_bit_identical": bool(np.array_equal(b_st, c_st)),
+                               "kernel": lik.compiled(64, linear=True).resources}
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--tune", type=int, default=10)
     ap.add_argument("--compiled-only", action="store_true", help="only the full-size compiled run (under a profiler)")
     ap.add_argument("--kvector-only", action="store_true", help="only the two K-vector legs")
+    ap.add_argument("--linear-only", action="store_true", help="only the two linear-leaf legs")
     args = ap.parse_args(argv)
     os.environ.setdefault("PGB_JIT_CACHE", tempfile.mkdtemp(prefix="pgb_jit_timing_"))  # (a fresh cache: a real compile)
     if args.kvector_only:
         print(json.dumps({"metric": "ms_per_astep", "tune": args.tune, "steps": args.steps,
                           **kvector_legs(args.tune, args.steps)}))
+        return 0
+    if args.linear_only:
+        print(json.dumps({"metric": "ms_per_astep", "tune": args.tune, "steps": args.steps,
+                          **linear_legs(args.tune, args.steps)}))
         return 0
     from pymc_bart_amd.compiled import CompiledLikelihood
 

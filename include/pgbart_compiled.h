@@ -45,7 +45,7 @@ typedef struct {
   int64_t sizeof_dev, sizeof_job, sizeof_cmd, sizeof_ctrl, sizeof_acc;
   uint64_t headers_hash;  /* PGB_HEADERS_HASH: a hash of the kernel headers (pymc_bart_amd/compiled.py) */
   int32_t linear_leaves;  /* 0: the constant-leaf pass, 1: the linear-leaf pass (response linear / mix) */
-  int32_t reserved_;      /* 0 */
+  int32_t pointwise;      /* 0: a sampler's pass kernel; 1: k_pointwise_compiled (pgbart_pointwise.h), no pass kernel */
 } pgb_compiled_layout;
 
 /* The params of one launch, by value (they arrive in SGPRs with the kernel arguments). */

@@ -1,0 +1,52 @@
+/*
+ * pgbart_pointwise.h -- scoring a fit: the pointwise log-likelihood of posterior draws at given rows, and its
+ * reduction over the draws (log pointwise predictive density, the WAIC terms), fused into the tree walk.
+ *
+ * Kept apart from pgbart.h like pgbart_compiled.h: pgbart.h is the ABI every backend (the CPU oracle included)
+ * exports in full; the entry point below exists in the HIP library only (both particle builds).  The numeric
+ * contract -- the densities, the clamp, the reduction -- is include/pgbart_logpdf.h.
+ */
+#ifndef PGBART_POINTWISE_H
+#define PGBART_POINTWISE_H
+
+#include <stdint.h>
+
+#include "pgbart.h"
+
+#define PGB_POINTWISE_KERNEL "k_pointwise_compiled"
+
+typedef struct {
+  int32_t family;             /* a built-in family of pgbart_spec.h, or PGB_FAMILY_COMPILED; the callback family is refused */
+  int32_t n_params;           /* params per draw: the family's (pgb_logpdf_nparams), or the compiled body's */
+  const double* params_host;  /* [n_forests][n_params], host memory (NULL when n_params = 0) */
+  const double* y_dev;        /* [n_rows] observed values, finite */
+  const double* offset_dev;   /* [K][n_rows] added to the predictors, |.| <= PGB_MAX_OFFSET, or NULL */
+  const double* aux_dev;      /* [n_rows] the compiled body's aux column, finite, or NULL (aux = 0.0) */
+  const void* code_object;    /* family compiled: a code object built with pointwise=True (pymc_bart_amd.compiled) ... */
+  int64_t code_bytes;         /* ... and its size; NULL / 0 otherwise */
+} pgb_pointwise_lik;
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* loglik[d][i] = clamp(log p(y[i] | mu_d(X[i,:]) + offset[.][i], params[d])) for the forests d (rows of
+ * forest_tree_idx, as pgb_predict takes them; no excluded variables) and the rows of X (device memory, row-major,
+ * leading dimension ldx).  mu_d is exactly what pgb_predict computes for the same arguments.
+ *   loglik_dev_out     [n_forests][n_rows], or NULL
+ *   row_stats_dev_out  [3][n_rows] = (lppd_i, mean_i, var_i) over the forests (pgbart_logpdf.h: the reduction), or
+ *                      NULL; with loglik_dev_out = NULL nothing of size n_forests x n_rows is written
+ *   n_clamped_out      the number of (forest, row) pairs whose value met the clamp (host memory, may be NULL)
+ * At least one of the two outputs must be given.  Everything is validated before a launch: PGB_E_INVALID for a
+ * malformed history, an unknown or callback family, a wrong n_params, params outside the family's domain, a K the
+ * family does not take, non-finite y / aux, an offset beyond PGB_MAX_OFFSET, or a code object that does not match
+ * (not built with pointwise=True, other headers, another n_params or K).  The call returns when the outputs are
+ * written.  PGB_PW_WGS (environment, read per call) overrides the number of workgroups aimed at, like PGB_PRED_WGS;
+ * results do not depend on it. */
+int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
+                         const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx, const pgb_pointwise_lik* lik,
+                         double* loglik_dev_out, double* row_stats_dev_out, int64_t* n_clamped_out, void* stream);
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* PGBART_POINTWISE_H */

@@ -13,6 +13,7 @@ from .compiled import CompiledLikelihood, CompileError, compile_loglik
 from .trees import PosteriorSampler, TreeArrays
 from .importance import compute_variable_importance, get_variable_inclusion, vi_to_kulprit
 from .partial import individual_conditional_expectation, partial_dependence
+from .pointwise import log_predictive_density, pointwise_log_likelihood
 
 
 def _register_step_method():
@@ -35,5 +36,5 @@ __version__ = "0.1.0"
 __all__ = [
     "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
-    "partial_dependence", "individual_conditional_expectation", "_abi",
+    "partial_dependence", "individual_conditional_expectation", "pointwise_log_likelihood", "log_predictive_density", "_abi",
 ]

@@ -148,6 +148,21 @@ class TreeArraysC(C.Structure):
     ]
 
 
+class PointwiseLik(C.Structure):
+    """``pgb_pointwise_lik`` (include/pgbart_pointwise.h)."""
+
+    _fields_ = [
+        ("family", C.c_int32),
+        ("n_params", C.c_int32),
+        ("params_host", C.c_void_p),
+        ("y_dev", C.c_void_p),
+        ("offset_dev", C.c_void_p),
+        ("aux_dev", C.c_void_p),
+        ("code_object", C.c_void_p),
+        ("code_bytes", C.c_int64),
+    ]
+
+
 #: ``pgb_loglik_fn``: int fn(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out)
 LOGLIK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.c_int64, C.POINTER(C.c_double))
@@ -233,6 +248,14 @@ class PGBLibrary:
         """``pgb_compiled_probe`` (include/pgbart_compiled.h): the loaded body evaluated on given rows."""
         f = self.lib.pgb_compiled_probe
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def pointwise_entry_point(self):
+        """``pgb_pointwise_loglik`` (include/pgbart_pointwise.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_pointwise_loglik
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.POINTER(PointwiseLik), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         f.restype = C.c_int
         return f
 

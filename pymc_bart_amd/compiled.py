@@ -15,7 +15,9 @@ checks the GPU chain bit for bit.  A body of ``n_outputs = K >= 2`` reads ``mu[0
 library's K-vector pass; no CPU backend runs it (the callback family has one output), and its host build is an
 evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is held to.  With ``linear=True`` the
 code object holds the library's linear-leaf pass instead (``response="linear"`` / ``"mix"``, one output or K): one pass
-kernel per code object, and HIP only -- the CPU backends' callback family has constant leaves.  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
+kernel per code object, and HIP only -- the CPU backends' callback family has constant leaves.  With ``pointwise=True``
+the code object holds no pass kernel but ``k_pointwise_compiled`` (``csrc/k_pointwise_compiled.hip``): the body inside
+the posterior tree walk, for scoring a fit (:mod:`pymc_bart_amd.pointwise`).  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
 everything that goes into them.
 """
 
@@ -38,6 +40,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 TU = os.path.join(CSRC, "k_loglik_compiled.hip")
+#: the unit of a POINTWISE code object (``compile_loglik(..., pointwise=True)``; include/pgbart_pointwise.h)
+TU_POINTWISE = os.path.join(CSRC, "k_pointwise_compiled.hip")
 LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 #: the library's device flags (``__graft_entry__.HIPCC_FLAGS`` without ``-fPIC`` / ``-shared``; a test holds them equal)
@@ -192,7 +196,7 @@ def uses_tables(body: str) -> bool:
 def _header_files() -> list[str]:
     files = [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
     files += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
-    return files + [TU]
+    return files + [TU, TU_POINTWISE]
 
 
 def headers_hash() -> int:
@@ -225,10 +229,12 @@ def cache_dir() -> str:
     return os.environ.get("PGB_JIT_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "pymc_bart_amd", "jit")
 
 
-def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1, linear: bool = False) -> str:
+def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1, linear: bool = False,
+              pointwise: bool = False) -> str:
     h = hashlib.sha256()
     h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
                          "n_outputs": int(n_outputs), "linear": bool(linear),
+                         **({"pointwise": True} if pointwise else {}),
                          "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
                          "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
                         sort_keys=True).encode())
@@ -350,8 +356,8 @@ def _compile_error(stderr: str, body: str, side: str) -> CompileError:
                         + f"\nthe vocabulary: {vocabulary_text()}")
 
 
-def kernel_resources(code_object_path: str) -> dict:
-    """VGPR / SGPR / scratch / LDS / spills / workgroups per CU of ``k_loglik_compiled``, from the code object's
+def kernel_resources(code_object_path: str, kernel: str = "k_loglik_compiled") -> dict:
+    """VGPR / SGPR / scratch / LDS / spills / workgroups per CU of ``kernel``, from the code object's
     metadata note -- the way tools/occupancy_guard.py reads the library's."""
     import yaml
 
@@ -360,7 +366,7 @@ def kernel_resources(code_object_path: str) -> dict:
     end = notes.index("\n...", start) if "\n..." in notes[start:] else len(notes)
     meta = yaml.safe_load(notes[start:end])
     for k in meta["amdhsa.kernels"]:
-        if k[".name"] == "k_loglik_compiled":  # (not the probe: its resources do not matter)
+        if k[".name"] == kernel:  # (not the probe: its resources do not matter)
             vg, ag = int(k[".vgpr_count"]), int(k.get(".agpr_count", 0))
             lds = int(k[".group_segment_fixed_size"])
             unified = ((vg + 3) // 4) * 4 + ag
@@ -371,7 +377,7 @@ def kernel_resources(code_object_path: str) -> dict:
                     "scratch_bytes": int(k[".private_segment_fixed_size"]),
                     "vgpr_spills": int(k.get(".vgpr_spill_count", 0)), "sgpr_spills": int(k.get(".sgpr_spill_count", 0)),
                     "wgs_per_cu": wgs}
-    raise CompileError("the code object has no kernel k_loglik_compiled")
+    raise CompileError(f"the code object has no kernel {kernel}")
 
 
 class CompiledLoglik:
@@ -381,10 +387,11 @@ class CompiledLoglik:
     constant leaves refuses it, and the other way round)."""
 
     def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached,
-                 n_outputs=1, linear=False):
+                 n_outputs=1, linear=False, pointwise=False):
         self.key, self.body, self.param_names, self.max_particles = key, body, tuple(param_names), int(max_particles)
         self.n_outputs = int(n_outputs)
         self.linear = bool(linear)
+        self.pointwise = bool(pointwise)  # the code object holds k_pointwise_compiled instead of a pass kernel
         self.code, self.host_lib, self.resources = code, host_lib, resources
         self.compile_seconds, self.cached = compile_seconds, cached
         self._host = None
@@ -441,6 +448,8 @@ class CompiledContext(C.Structure):
 
 
 def _warn_scratch(b: "CompiledLoglik") -> None:
+    if b.pointwise:  # (the walk's own stack of the marginalising path lives in scratch: nothing about the body)
+        return
     if (b.n_outputs > 1 or b.linear) and b.resources.get("scratch_bytes", 0) > 0:
         warnings.warn(f"the likelihood body of {b.n_outputs} outputs{' (linear leaves)' if b.linear else ''} puts "
                       f"{b.resources['scratch_bytes']} B per thread "
@@ -450,15 +459,22 @@ def _warn_scratch(b: "CompiledLoglik") -> None:
 
 
 def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1,
-                   linear: bool = False) -> CompiledLoglik:
+                   linear: bool = False, pointwise: bool = False) -> CompiledLoglik:
     """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
     (64 or 128) and ``n_outputs`` predictors -- or take it from the cache.  ``linear``: the code object's pass is
-    the linear-leaf one (``response="linear"`` / ``"mix"``) instead of the constant-leaf one."""
+    the linear-leaf one (``response="linear"`` / ``"mix"``) instead of the constant-leaf one.  ``pointwise``: a code
+    object of its own kind -- no pass kernel but ``k_pointwise_compiled``, the body inside the posterior tree walk
+    (:mod:`pymc_bart_amd.pointwise`); it serves every kind of leaves and either particle build."""
     K = check_outputs(n_outputs)
     names = validate(body, param_names, K)
     mp = 128 if int(max_particles) > 64 else 64
     linear = bool(linear)
-    key = cache_key(body, names, mp, K, linear)
+    pointwise = bool(pointwise)
+    if pointwise:
+        if linear:
+            raise ValueError("pointwise=True takes no linear=True: the walk applies the leaves' slopes itself")
+        mp = 64  # (the kernel reads no particle record: one object for both builds)
+    key = cache_key(body, names, mp, K, linear, pointwise)
     root = cache_dir()
     os.makedirs(root, exist_ok=True)
     co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
@@ -467,7 +483,7 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
             meta = json.load(fh)
         with open(co_path, "rb") as fh:
             code = fh.read()
-        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K, linear)
+        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K, linear, pointwise)
         _warn_scratch(b)
         return b
     t0 = time.perf_counter()
@@ -487,11 +503,11 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
             fh.write(_body_text(body))
         co_tmp = os.path.join(tmp, "k.co")
         cmd = [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, f"-DPGB_MAX_PARTICLES={mp}", f"-I{CSRC}", f"-I{tmp}", "-w",
-               TU, "-o", co_tmp]
+               TU_POINTWISE if pointwise else TU, "-o", co_tmp]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise _compile_error(r.stderr, body, "device")
-        resources = kernel_resources(co_tmp)
+        resources = kernel_resources(co_tmp, "k_pointwise_compiled" if pointwise else "k_loglik_compiled")
         seconds = time.perf_counter() - t0
         with open(co_tmp, "rb") as fh:
             code = fh.read()
@@ -499,10 +515,11 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
             host = fh.read()
     _write_atomic(co_path, code)
     _write_atomic(so_path, host)
-    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "linear": linear, "resources": resources,
+    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "linear": linear, "pointwise": pointwise,
+            "resources": resources,
             "compile_seconds": seconds}
     _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
-    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K, linear)
+    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K, linear, pointwise)
     _warn_scratch(b)
     return b
 
@@ -552,11 +569,12 @@ class CompiledLikelihood:
         self._builds = {}
         self.compiled(64)  # (errors surface here, not at the first step)
 
-    def compiled(self, max_particles: int = 64, linear: bool = False) -> CompiledLoglik:
-        mp = 128 if int(max_particles) > 64 else 64
-        k = (mp, bool(linear))
+    def compiled(self, max_particles: int = 64, linear: bool = False, pointwise: bool = False) -> CompiledLoglik:
+        mp = 128 if int(max_particles) > 64 and not pointwise else 64
+        k = (mp, False, True) if pointwise else (mp, bool(linear))
         if k not in self._builds:
-            self._builds[k] = compile_loglik(self.body, self.param_names, mp, self.n_outputs, bool(linear))
+            self._builds[k] = compile_loglik(self.body, self.param_names, mp, self.n_outputs, bool(linear),
+                                             bool(pointwise))
         return self._builds[k]
 
     def params(self, point=None):

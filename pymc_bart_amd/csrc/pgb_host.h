@@ -1437,13 +1437,11 @@ extern "C" int pgb_get_split_weights(pgb_handle* h, double* out) {
   return PGB_OK;
 }
 
-extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests,
-                           int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
-                           const int32_t* excluded_host, int32_t n_excluded,
-                           double* out_dev, void* stream) {
-  if (!trees || !forest_tree_idx || !X_dev || !out_dev) return fail(PGB_E_INVALID, "null argument");
+// The history of a prediction (pgb_predict, pgb_pointwise_loglik), checked: a malformed one (truncated file,
+// mismatched m) is an error, not an out-of-bounds walk.
+static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
+                         int32_t p) {
   if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
-  if (n_forests < 1 || n_rows < 1) return PGB_OK;
   // a malformed history (truncated file, mismatched m) is an error, not an out-of-bounds walk
   if (trees->n_trees < 0 || trees->total_nodes < 0) return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
   for (long long i = 0; i < (long long)n_forests * m; ++i)
@@ -1463,7 +1461,18 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
         return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
     }
   }
-  hipStream_t sm = (hipStream_t)stream;
+  return PGB_OK;
+}
+
+// ... and packed into ONE upload (freed by the caller: pk->db) for the walk of pgb_pred_walk.h
+struct PredPack {
+  uint8_t* db = nullptr;
+  PredTrees T;
+  const int32_t* fidx = nullptr;  // [n_forests][m], device
+  bool cont = true;               // every split of every tree is `x <= v`: the instances without the rule dispatch
+};
+static int pred_pack(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m, int32_t p,
+                     const int32_t* excluded_host, int32_t n_excluded, hipStream_t sm, PredPack* pk) {
   const int K = trees->n_outputs, N = trees->total_nodes, NT = trees->n_trees;
   std::vector<uint8_t> excl((size_t)p, 0);
   for (int e = 0; e < n_excluded; ++e)
@@ -1540,7 +1549,7 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
   HIPCHK(hipMalloc((void**)&db, bytes));
   hipError_t e = hipMemcpyAsync(db, hb.data(), bytes, hipMemcpyHostToDevice, sm);
   if (e != hipSuccess) { (void)hipFree(db); return fail_hip(e, "hipMemcpyAsync"); }
-  PredTrees T;
+  PredTrees& T = pk->T;
   T.node = (const PNode*)db;
   T.value = (const double*)(db + o_val);
   T.slope = lin ? (const double*)(db + o_slope) : nullptr;
@@ -1548,6 +1557,29 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
   T.fnode = (const FNode*)(db + o_fn);
   T.root = (const int2*)(db + o_root);
   T.svar = lin ? (const int32_t*)(db + o_svar) : nullptr;
+  pk->db = db;
+  pk->fidx = (const int32_t*)(db + o_f);
+  pk->cont = cont;
+  return PGB_OK;
+}
+
+extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests,
+                           int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
+                           const int32_t* excluded_host, int32_t n_excluded,
+                           double* out_dev, void* stream) {
+  if (!trees || !forest_tree_idx || !X_dev || !out_dev) return fail(PGB_E_INVALID, "null argument");
+  if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
+  if (n_forests < 1 || n_rows < 1) return PGB_OK;
+  int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
+  if (rc != PGB_OK) return rc;
+  hipStream_t sm = (hipStream_t)stream;
+  PredPack pk;
+  rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, excluded_host, n_excluded, sm, &pk);
+  if (rc != PGB_OK) return rc;
+  const int K = trees->n_outputs;
+  const PredTrees T = pk.T;
+  uint8_t* db = pk.db;
+  const bool cont = pk.cont;
   // one wave per workgroup; enough workgroups to fill the chip, each looping over its share of forests
   const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
   long long want_wgs = p <= PRED_LDS_MAXP ? 16384 : 4096;  // measured at cfg2 (32 forests x 100k rows): 10.0 vs 11.7 ms
@@ -1557,7 +1589,7 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
   if (gy < 1) gy = 1;
   dim3 grid((unsigned)gx, (unsigned)gy);
 #define LAUNCH_PRED(L_, C_, LDS_)                                                                               \
-  hipLaunchKernelGGL((k_predict<L_, C_>), grid, dim3(PRED_BT), (LDS_), sm, T, (const int32_t*)(db + o_f), n_forests, \
+  hipLaunchKernelGGL((k_predict<L_, C_>), grid, dim3(PRED_BT), (LDS_), sm, T, pk.fidx, n_forests, \
                      m, K, (int)p, X_dev, (long long)n_rows, (long long)ldx, out_dev)
   const size_t lds = (size_t)p * 65 * sizeof(double);
   if (p <= PRED_LDS_MAXP) {
@@ -1568,7 +1600,7 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
     else LAUNCH_PRED(false, false, 0);
   }
 #undef LAUNCH_PRED
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   hipError_t e2 = hipStreamSynchronize(sm);
   (void)hipFree(db);
   if (e != hipSuccess) return fail_hip(e, "k_predict launch");

@@ -46,6 +46,8 @@
 #include "pgbart_pack.h"
 #include "pgbart_spec.h"
 #include "pgbart_compiled.h"  // (family 11: its code object is compiled at run time, k_loglik_compiled.hip)
+#include "pgbart_logpdf.h"
+#include "pgbart_pointwise.h"
 
 #include "pgb_dims.h"
 
@@ -57,8 +59,11 @@
 #include "k_rows.h"
 #include "k_rows_mk.h"
 #include "k_loglik.h"
+#include "pgb_pred_walk.h"
 #include "k_setup_predict.h"
+#include "k_pointwise.h"
 #include "k_export.h"
 #include "pgb_host.h"
 #include "pgb_checkpoint.h"
 #include "pgb_probe.h"
+#include "pgb_pointwise_host.h"

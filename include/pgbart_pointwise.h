@@ -45,6 +45,17 @@ extern "C" {
 int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
                          const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx, const pgb_pointwise_lik* lik,
                          double* loglik_dev_out, double* row_stats_dev_out, int64_t* n_clamped_out, void* stream);
+
+/* PSIS-LOO of the rows of such a matrix (the numeric contract is include/pgbart_psis.h: Pareto-smoothed importance
+ * sampling of each row's values over the draws).  ll_dev is [D][ld] device memory as pgb_pointwise_loglik writes it
+ * (finite values within [-2047, 2047]; the first n_rows of every ld are read), tail_len the number of largest
+ * importance ratios that are smoothed, M = ceil(min(D / 5, 3 sqrt(D / r_eff))), computed by the caller.
+ *   out_dev  [2][n_rows] = (elpd_loo_i, k_i); k_i = +inf where no generalised-Pareto fit was possible
+ * Everything is validated before the launch: PGB_E_INVALID unless 2 <= D <= PGB_PSIS_MAX_DRAWS (16384),
+ * 1 <= tail_len < D, tail_len <= PGB_PSIS_MAX_TAIL (448) and ld >= n_rows >= 1.  The call returns when the output is
+ * written.  HIP library only (both particle builds). */
+int pgb_psis_rows(const double* ll_dev, int32_t D, int64_t n_rows, int64_t ld, int32_t tail_len, double* out_dev,
+                  void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -259,6 +259,13 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def psis_entry_point(self):
+        """``pgb_psis_rows`` (include/pgbart_pointwise.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_psis_rows
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     @property
     def backend_name(self) -> str:
         return self.lib.pgb_backend_name().decode()

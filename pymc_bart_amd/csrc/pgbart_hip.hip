@@ -48,6 +48,7 @@
 #include "pgbart_compiled.h"  // (family 11: its code object is compiled at run time, k_loglik_compiled.hip)
 #include "pgbart_logpdf.h"
 #include "pgbart_pointwise.h"
+#include "pgbart_psis.h"
 
 #include "pgb_dims.h"
 
@@ -67,3 +68,4 @@
 #include "pgb_checkpoint.h"
 #include "pgb_probe.h"
 #include "pgb_pointwise_host.h"
+#include "k_psis.h"

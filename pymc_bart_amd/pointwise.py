@@ -159,8 +159,10 @@ class _Job:
         self.likelihood = likelihood
         self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None
 
-    def run(self, matrix: bool, summary: bool):
-        """-> (matrix (D, n) or None, row_stats (3, n) or None, n_clamped)"""
+    def run(self, matrix: bool, summary: bool, on_block=None):
+        """-> (matrix (D, n) or None, row_stats (3, n) or None, n_clamped).  ``on_block(lib, mem, md, nb, r0)``: called
+        with every block's matrix still on the device (``md``: ``[D][nb]``, rows ``r0 .. r0 + nb``) in place of its
+        copy to the host -- nothing of size draws x rows then leaves the device (:mod:`pymc_bart_amd.loo`)."""
         from .sampler import default_backend
 
         be = self.backend() if self.backend is not None else default_backend()
@@ -178,9 +180,10 @@ class _Job:
             build = self.likelihood.compiled(pointwise=True)
             code = C.create_string_buffer(build.code, len(build.code))
             lik.code_object, lik.code_bytes = C.cast(code, C.c_void_p), len(build.code)
-        per_row = 8 * (p + 2 + K + (D if matrix else 4 * (-(-D // CHUNK)) + 3))
+        per_row = 8 * (p + 2 + K + (D if matrix else 0) + (4 * (-(-D // CHUNK)) + 3 if summary else 0)
+                       + (2 if on_block is not None else 0))
         block = max(64, min(n, _block_bytes() // per_row // 64 * 64))
-        out = np.empty((D, n)) if matrix else None
+        out = np.empty((D, n)) if matrix and on_block is None else None
         stats = np.empty((3, n)) if summary else None
         carr = self.pool.as_c()
         clamped = 0
@@ -202,7 +205,9 @@ class _Job:
                       mem.stream_ptr)
             lib.check(rc, "pgb_pointwise_loglik")
             clamped += int(nc.value)
-            if matrix:
+            if on_block is not None:
+                on_block(lib, mem, md, nb, r0)
+            elif matrix:
                 out[:, r0:r1] = mem.to_host(md).reshape(D, nb)
             if summary:
                 stats[:, r0:r1] = mem.to_host(sd).reshape(3, nb)

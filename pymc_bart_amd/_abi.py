@@ -266,6 +266,15 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def ice_entry_point(self):
+        """``pgb_predict_ice`` (include/pgbart_ice.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_predict_ice
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     @property
     def backend_name(self) -> str:
         return self.lib.pgb_backend_name().decode()

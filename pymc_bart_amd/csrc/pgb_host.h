@@ -1563,6 +1563,41 @@ static int pred_pack(const pgb_tree_arrays* trees, const int32_t* forest_tree_id
   return PGB_OK;
 }
 
+// PGB_WALK_TIMING=1 (environment, read per call): the walk kernel of pgb_predict / pgb_predict_ice alone, between two
+// HIP events on the call's stream; pgb_walk_kernel_ms (include/pgbart_ice.h) reports the last one of the calling
+// thread (tools/ice_timing.py).  Unset: no event is created.
+static thread_local double g_walk_ms = -1.0;
+struct WalkTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t sm;
+  explicit WalkTimer(hipStream_t s) : sm(s) {
+    const char* ev = getenv("PGB_WALK_TIMING");
+    if (!ev || atoi(ev) <= 0) return;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, sm) != hipSuccess) {
+      (void)hipGetLastError();
+      drop();
+    }
+  }
+  void launched() {
+    if (a && hipEventRecord(b, sm) != hipSuccess) drop();
+  }
+  void synced() {  // (after the stream has been synchronised)
+    float ms = 0.f;
+    if (a && hipEventElapsedTime(&ms, a, b) == hipSuccess) g_walk_ms = (double)ms;
+  }
+  void drop() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+    a = b = nullptr;
+  }
+  ~WalkTimer() { drop(); }
+};
+extern "C" int pgb_walk_kernel_ms(double* ms_out) {
+  if (!ms_out) return fail(PGB_E_INVALID, "null argument");
+  *ms_out = g_walk_ms;
+  return PGB_OK;
+}
+
 extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests,
                            int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
                            const int32_t* excluded_host, int32_t n_excluded,
@@ -1592,6 +1627,7 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
   hipLaunchKernelGGL((k_predict<L_, C_>), grid, dim3(PRED_BT), (LDS_), sm, T, pk.fidx, n_forests, \
                      m, K, (int)p, X_dev, (long long)n_rows, (long long)ldx, out_dev)
   const size_t lds = (size_t)p * 65 * sizeof(double);
+  WalkTimer wt(sm);
   if (p <= PRED_LDS_MAXP) {
     if (cont) LAUNCH_PRED(true, true, lds);
     else LAUNCH_PRED(true, false, lds);
@@ -1601,7 +1637,9 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
   }
 #undef LAUNCH_PRED
   hipError_t e = hipGetLastError();
+  wt.launched();
   hipError_t e2 = hipStreamSynchronize(sm);
+  if (e == hipSuccess && e2 == hipSuccess) wt.synced();
   (void)hipFree(db);
   if (e != hipSuccess) return fail_hip(e, "k_predict launch");
   if (e2 != hipSuccess) return fail_hip(e2, "k_predict");

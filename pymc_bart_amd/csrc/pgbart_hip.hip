@@ -49,6 +49,7 @@
 #include "pgbart_logpdf.h"
 #include "pgbart_pointwise.h"
 #include "pgbart_psis.h"
+#include "pgbart_ice.h"
 
 #include "pgb_dims.h"
 
@@ -69,3 +70,4 @@
 #include "pgb_probe.h"
 #include "pgb_pointwise_host.h"
 #include "k_psis.h"
+#include "k_ice.h"

@@ -5,7 +5,8 @@ The reference computes these inside its plotting functions (``plot_pdp`` ``utils
 the numbers are not: they are sweeps of posterior predictions -- per covariate ``samples x m x grid``
 tree traversals with every OTHER covariate marginalised out by the trees' own training counts
 (``excluded``) for the PDP, and ``instances x samples x m x n`` traversals for ICE -- i.e. work for
-the ``k_predict`` kernel behind ``PosteriorSampler.sample_posterior``.
+the ``k_predict`` kernel behind ``PosteriorSampler.sample_posterior`` (the PDP) and for ``k_ice`` behind
+``PosteriorSampler.ice_mean`` (ICE: every curve of a sweep from one fused call).
 
 What the functions return is exactly what upstream hands to its axes: per covariate the grid
 ``x`` and the array of predictions; random draws follow the same call pattern (one
@@ -89,22 +90,31 @@ def individual_conditional_expectation(bart, X, var_idx=None, instances: int = 3
     """ICE curves: for each of ``instances`` randomly chosen rows, the posterior-mean prediction
     along the observed values of covariate ``j`` with all other covariates held at that row's
     values.  Returns ``{"x": {j: X[:, j]}, "ice": {j: array (instances, n, outputs)}, "labels"}``;
-    ``centered`` subtracts each curve's value at the first row, as the upstream plot does."""
+    ``centered`` subtracts each curve's value at the first row, as the upstream plot does.
+
+    The draws of every curve are chosen first -- one ``rng.integers(0, n_draws, samples)`` per (covariate,
+    instance), in that order -- and all curves then come from ONE ``ice_mean`` call per sampler: no probe matrix is
+    built (``include/pgbart_ice.h``).  A list of BART variables contributes its outputs side by side, from the
+    same draws."""
     Xm, names = _as_matrix(X)
     n, p = Xm.shape
     cols = list(range(p)) if var_idx is None else [int(v) for v in var_idx]
     sampler = _samplers(bart, backend)
+    group = sampler if isinstance(sampler, list) else [sampler]
     rng = np.random.default_rng(random_seed)
     chosen = rng.choice(n, replace=False, size=min(int(instances), n))
     out = {"x": {}, "ice": {}, "labels": {}, "instances": chosen}
-    for j in cols:
-        others = [v for v in range(p) if v != j]
-        curves = []
-        for row in chosen:
-            probe = Xm.copy()
-            probe[:, others] = Xm[row, others]
-            curves.append(_sample_posterior(sampler, X=probe, rng=rng, size=samples).mean(axis=0))
-        ice_j = np.asarray(curves)
+    if not cols:
+        return out
+    picks = np.empty((len(cols), len(chosen), int(samples)), np.int64)
+    for c in range(len(cols)):
+        for r in range(len(chosen)):
+            picks[c, r] = rng.integers(0, group[0].n_draws, size=int(samples))
+    rows = _resident_rows(sampler, Xm) if len(group) > 1 else Xm  # (several samplers: one upload for all of them)
+    blocks = [g.ice_mean(rows, Xm[chosen], cols, picks) for g in group]  # (n_cols, n_inst, K_g, n)
+    stacked = blocks[0] if len(blocks) == 1 else np.concatenate(blocks, axis=2)
+    for c, j in enumerate(cols):
+        ice_j = np.ascontiguousarray(np.moveaxis(stacked[c], 1, 2))  # (n_inst, n, K)
         if func is not None:
             ice_j = func(ice_j)
         if centered:

@@ -145,16 +145,10 @@ class _Job:
             raise ValueError("no draws to score")
         self.D = D = int(idx.size)
         self.params = _param_matrix(likelihood, points, D)
-        if len(parts) == 1:
-            self.pool = parts[0].pool
-            table = parts[0].forest_idx
-        else:
-            from .trees import TreeArrays
+        from .trees import pooled_history
 
-            pools = [part.pool.decoded() if hasattr(part.pool, "decoded") else part.pool for part in parts]
-            self.pool = TreeArrays.concat(pools)
-            shift = np.concatenate([[0], np.cumsum([pl.n_trees for pl in pools])])
-            table = np.concatenate([part.forest_idx.astype(np.int64) + shift[c] for c, part in enumerate(parts)])
+        cached = getattr(sampler, "pooled_history", None)  # (the multi-chain sampler keeps it)
+        self.pool, table = cached() if cached is not None else pooled_history(parts)
         self.fidx = np.ascontiguousarray(np.asarray(table)[idx], dtype=np.int32)
         self.likelihood = likelihood
         self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None

@@ -310,6 +310,19 @@ def predict_numpy(trees: TreeArrays, forest_idx: np.ndarray, X: np.ndarray, excl
     return out
 
 
+def pooled_history(parts: list) -> tuple:
+    """The chains of one BART variable as ONE history: ``(pool, table)``, the concatenated tree pool and the forest
+    table of every chain shifted into it, in chain order (row ``d`` is draw ``d`` of the concatenated history).  One
+    chain: its own pool and table."""
+    if len(parts) == 1:
+        return parts[0].pool, parts[0].forest_idx
+    pools = [part.pool.decoded() if hasattr(part.pool, "decoded") else part.pool for part in parts]
+    pool = TreeArrays.concat(pools)
+    shift = np.concatenate([[0], np.cumsum([pl.n_trees for pl in pools])])
+    table = np.concatenate([part.forest_idx.astype(np.int64) + shift[c] for c, part in enumerate(parts)])
+    return pool, table
+
+
 class PosteriorSampler:
     """Prediction-only sampler rebuilt from one chain's tree history.
 
@@ -391,3 +404,15 @@ class PosteriorSampler:
         )
         be.lib.check(rc, "pgb_predict")
         return be.mem.to_host(outd).reshape(fidx.shape[0], K, n_rows)
+
+    def ice_mean(self, X, instances, cols, picks) -> np.ndarray:
+        """Individual conditional expectation curves, ``(n_cols, n_inst, n_outputs, n_rows)``: entry ``[c, r, k, i]``
+        is the mean over the draws ``picks[c, r, :]`` of output ``k`` predicted at ``instances[r]`` with its column
+        ``cols[c]`` replaced by ``X[i, cols[c]]`` -- summed in pick order, divided once.  ``X`` may be a handle from
+        :meth:`resident_rows`; ``instances`` is ``(n_inst, p)``, ``picks`` ``(n_cols, n_inst, n_picks)`` draw indices
+        (they may repeat).  On the HIP backend this is one fused ``pgb_predict_ice`` call per block of columns (the
+        device output stays under ``PGB_ICE_BLOCK_BYTES``, default 1 GiB; results do not depend on the blocking)."""
+        from .ice import ice_mean
+
+        return ice_mean(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, self.sample_posterior,
+                        X, instances, cols, picks)

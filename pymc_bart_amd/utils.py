@@ -11,7 +11,7 @@ import base64
 
 import numpy as np
 
-from .trees import PosteriorSampler
+from .trees import PosteriorSampler, pooled_history
 
 
 def _encode_vi(vec) -> str:
@@ -98,6 +98,7 @@ class _MultiChainSampler:
         if not self._parts:
             raise ValueError("No posterior draws available yet: run the sampler first.")
         self._starts = np.concatenate([[0], np.cumsum([part.n_draws for part in self._parts])]).astype(np.int64)
+        self._pooled = None
 
     @property
     def _chain_samplers(self):  # name used by callers that reach into the chains
@@ -110,6 +111,22 @@ class _MultiChainSampler:
     @property
     def n_outputs(self) -> int:
         return self._parts[0].n_outputs
+
+    def pooled_history(self) -> tuple:
+        """``(pool, table)`` of all chains as one history (``trees.pooled_history``), built once."""
+        if self._pooled is None:
+            self._pooled = pooled_history(self._parts)
+        return self._pooled
+
+    def ice_mean(self, X, instances, cols, picks) -> np.ndarray:
+        """``PosteriorSampler.ice_mean`` over the concatenated history: ``picks`` index the draws of all chains, and
+        the pick-order sum of a curve may cross chains."""
+        from .ice import ice_mean
+
+        first = self._parts[0]
+        pool, table = self.pooled_history()
+        return ice_mean(first._get_backend(), pool, table, first.m, first.n_outputs, self.sample_posterior,
+                        X, instances, cols, picks)
 
     def sample_posterior(self, X, draw_indices, excluded):
         want = np.asarray(draw_indices, dtype=np.int64).ravel()

@@ -275,6 +275,14 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def rowsummary_entry_point(self):
+        """``pgb_row_summary`` (include/pgbart_rowsummary.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_row_summary
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     @property
     def backend_name(self) -> str:
         return self.lib.pgb_backend_name().decode()

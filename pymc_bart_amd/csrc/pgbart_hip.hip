@@ -50,6 +50,7 @@
 #include "pgbart_pointwise.h"
 #include "pgbart_psis.h"
 #include "pgbart_ice.h"
+#include "pgbart_rowsummary.h"
 
 #include "pgb_dims.h"
 
@@ -71,3 +72,4 @@
 #include "pgb_pointwise_host.h"
 #include "k_psis.h"
 #include "k_ice.h"
+#include "k_rowsummary.h"

@@ -53,27 +53,67 @@ def _samplers(bart, backend):
     return got if isinstance(bart, list) else got[0]
 
 
+def _summarised(sampler, grid, rng, samples: int, others, spec):
+    """One covariate of :func:`partial_dependence` with ``summary=``: the predictions ``(samples, grid, outputs)`` of
+    the draws ``_sample_posterior`` would pick (the same single ``rng.integers`` call) and their device summary."""
+    from .summary import _Job
+
+    group = sampler if isinstance(sampler, list) else [sampler]
+    picks = rng.integers(0, group[0].n_draws, size=samples)
+    got = [_Job(g, grid, picks, spec[0], spec[1], spec[2], None, others).run(keep_matrix=True) for g in group]
+    pred = got[0][1] if len(got) == 1 else np.concatenate([g[1] for g in got], axis=1)  # (samples, K, grid)
+    res = dict(got[0][0])
+    if len(got) > 1:  # a list of samplers contributes its outputs side by side
+        for key in ("mean", "sd", "var", "quantiles", "hdi"):
+            if res[key] is not None:
+                res[key] = np.concatenate([g[0][key] for g in got], axis=-1)
+    return np.ascontiguousarray(np.moveaxis(pred, 1, 2)), res
+
+
 def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs_values=None,
-                       samples: int = 200, func=None, random_seed=None, backend=None) -> dict:
+                       samples: int = 200, func=None, random_seed=None, backend=None, summary=None) -> dict:
     """Partial dependence of the BART function on each covariate of ``var_idx``.
 
     For covariate ``j`` the forest is evaluated on the grid with all other covariates excluded:
     at a split on an excluded covariate a tree answers with the count-weighted mean of both
     subtrees, which is BART's own marginalisation.  Returns ``{"x": {j: grid_j}, "pd": {j: array
     (samples, grid, outputs)}, "labels": {j: name}, "reference": mean of all partial dependences}``
-    (the dashed reference line of the upstream plot)."""
+    (the dashed reference line of the upstream plot).
+
+    ``summary={"quantiles": ..., "hdi_prob": ..., "transform": ...}`` (every key optional) adds ``out["summary"][j]``:
+    the mean, sd, var, quantiles and HDI of ``pd[j]`` over its samples -- arrays ``(grid, outputs)`` -- computed on
+    the device from the same draws by :func:`~pymc_bart_amd.posterior_summary`'s kernel, one predict-plus-summary
+    call per covariate.  ``func`` is a host function and cannot be combined with it: name a ``transform``."""
+    spec = None
+    if summary is not None:
+        if func is not None:
+            raise ValueError("func cannot be combined with summary=: the summary is computed on the device "
+                             "(use summary={'transform': ...})")
+        unknown = set(summary) - {"quantiles", "hdi_prob", "transform"}
+        if unknown:
+            raise ValueError(f"summary takes the keys quantiles, hdi_prob and transform, got {sorted(unknown)}")
+        from . import summary as _summary
+
+        spec = (summary.get("quantiles", _summary.DEFAULT_QUANTILES), summary.get("hdi_prob", _summary.DEFAULT_HDI_PROB),
+                summary.get("transform", "identity"))
+        _summary._spec(int(samples), *spec)  # (refused before a backend is touched)
     Xm, names = _as_matrix(X)
     p = Xm.shape[1]
     cols = list(range(p)) if var_idx is None else [int(v) for v in var_idx]
     sampler = _samplers(bart, backend)
     rng = np.random.default_rng(random_seed)
     grid = pdp_grid(Xm, xs_interval, xs_values)
-    rows = _resident_rows(sampler, grid)  # one upload for the sweep over the covariates
+    rows = _resident_rows(sampler, grid) if spec is None else None  # one upload for the sweep over the covariates
     out = {"x": {}, "pd": {}, "labels": {}, "reference": None}
+    if spec is not None:
+        out["summary"] = {}
     means = []
     for j in cols:
         others = [v for v in range(p) if v != j]
-        pd_j = _sample_posterior(sampler, X=rows, rng=rng, size=samples, excluded=others)
+        if spec is not None:
+            pd_j, out["summary"][j] = _summarised(sampler, grid, rng, int(samples), others, spec)
+        else:
+            pd_j = _sample_posterior(sampler, X=rows, rng=rng, size=samples, excluded=others)
         if func is not None:
             pd_j = func(pd_j)
         out["x"][j] = grid[:, j]

@@ -1,0 +1,209 @@
+"""Reading a fit: per-row summaries of the posterior predictions on the device (``pgb_row_summary``,
+``include/pgbart_rowsummary.h``).
+
+What every notebook ends in -- ``pred.mean(0)``, ``np.quantile(pred, q, 0)``, ``az.hdi(pred)`` -- without the
+``(draws, K, rows)`` array leaving the device: per block of rows one ``pgb_predict`` call writes the predictions of
+all draws into device scratch and one ``pgb_row_summary`` call sorts every column over its draws and reads the mean,
+the variance, the quantiles and the highest-density interval out of it.
+
+* :func:`posterior_summary` summarises the predictions of a fit at the rows of ``X``.
+* :func:`summarize_matrix` takes a ``(D, n)`` matrix the caller already has on the host.
+
+HIP backend only.  Between 2 and :data:`MAX_DRAWS` draws, at most :data:`MAX_QUANTILES` quantiles per call.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _abi
+from .pointwise import MAX_OFFSET, _block_bytes, _chains
+
+MAX_DRAWS = 16384    # PGB_ROWSUM_MAX_DRAWS (include/pgbart_rowsummary.h)
+MAX_QUANTILES = 16   # PGB_ROWSUM_MAX_Q
+TRANSFORMS = {"identity": 0, "exp": 1, "logistic": 2, "probit": 3}  # PGB_ROWSUM_*
+DEFAULT_QUANTILES = (0.03, 0.5, 0.97)
+DEFAULT_HDI_PROB = 0.94
+
+
+def hdi_length(D: int, prob) -> int:
+    """``max(floor(prob D), 1)``: the sorted draws ``i`` and ``i + hdi_length`` bound the candidate intervals
+    (``importance.hdi``); 0 for ``prob=None`` (no interval)."""
+    if prob is None:
+        return 0
+    prob = float(prob)
+    if not (0.0 < prob <= 1.0):
+        raise ValueError(f"hdi_prob must be in (0, 1] or None, got {prob!r}")
+    return max(int(math.floor(prob * int(D))), 1)
+
+
+def _spec(D: int, quantiles, hdi_prob, transform):
+    """-> (q array, hdi_k, transform code) of one call, checked."""
+    if transform not in TRANSFORMS:
+        raise ValueError(f"unknown transform {transform!r}: use one of {', '.join(TRANSFORMS)}")
+    q = np.asarray([] if quantiles is None else quantiles, dtype=np.float64)
+    if q.ndim != 1:
+        raise ValueError(f"quantiles must be a vector of levels, got shape {q.shape}")
+    if q.size > MAX_QUANTILES:
+        raise ValueError(f"at most {MAX_QUANTILES} quantiles per call, got {q.size}")
+    if q.size and not np.all((q >= 0.0) & (q <= 1.0)):  # (a NaN fails both comparisons)
+        raise ValueError("quantiles must be in [0, 1]")
+    D = int(D)
+    if D < 2:
+        raise ValueError(f"a summary over the draws needs at least 2 draws, got {D}")
+    if D > MAX_DRAWS:
+        raise ValueError(f"a summary on the device takes at most {MAX_DRAWS} draws, got {D} (thin them: draws=)")
+    return np.ascontiguousarray(q), hdi_length(D, hdi_prob), TRANSFORMS[transform]
+
+
+def _hip(backend):
+    from .sampler import default_backend
+
+    be = backend if backend is not None else default_backend()
+    if be.lib.backend_name != "hip-gfx950":
+        raise _abi.PGBError(f"posterior summaries run on the HIP backend only, not on {be.lib.backend_name}")
+    return be
+
+
+def _summary_block(lib, mem, md, D: int, n_cols: int, ld: int, od, code: int, q: np.ndarray, hdi_k: int) -> np.ndarray:
+    """``(2 + Q + 2, n_cols)`` of the device matrix ``md`` ``[D][ld]`` (``od``: the columns' offsets on the device)."""
+    rows = 2 + q.size + 2
+    sd = mem.empty((rows * n_cols,), np.float64)
+    rc = lib.rowsummary_entry_point()(mem.ptr(md), D, n_cols, ld, None if od is None else mem.ptr(od), code,
+                                      q.ctypes.data if q.size else None, int(q.size), int(hdi_k), mem.ptr(sd), mem.stream_ptr)
+    lib.check(rc, "pgb_row_summary")
+    return mem.to_host(sd).reshape(rows, n_cols)
+
+
+def _result(stats: np.ndarray, n: int, K: int, q: np.ndarray, hdi_prob, hdi_k: int, D: int) -> dict:
+    """``stats`` ``(2 + Q + 2, K, n)`` -> the public dict (arrays ``(..., n, K)``)."""
+    by = np.ascontiguousarray(np.moveaxis(stats.reshape(-1, K, n), 1, 2))  # (rows, n, K)
+    Q = q.size
+    var = by[1].copy()
+    return {"mean": by[0].copy(), "sd": np.sqrt(var), "var": var, "quantiles": by[2:2 + Q].copy(),
+            "hdi": by[2 + Q:4 + Q].copy() if hdi_k else None, "q": q.copy(),
+            "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": int(D)}
+
+
+class _Job:
+    """Everything of one :func:`posterior_summary` call, validated on the host before a backend is touched."""
+
+    def __init__(self, sampler, X, draws, quantiles, hdi_prob, transform, offset, excluded):
+        parts = _chains(sampler)
+        self.K = K = int(parts[0].n_outputs)
+        self.m = int(parts[0].m)
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError(f"X must be a matrix (n_rows, p), got shape {X.shape}")
+        self.X = np.ascontiguousarray(X)
+        n, p = self.n, self.p = int(X.shape[0]), int(X.shape[1])
+        self.offset = None
+        if offset is not None:
+            off = np.asarray(offset, dtype=np.float64)
+            if off.shape == (n,) and K == 1:
+                off = off[None, :]
+            if off.shape != (K, n):
+                raise ValueError(f"offset must have shape (n_outputs, n_rows) = ({K}, {n}), got {off.shape}")
+            if not np.all(np.isfinite(off)) or np.max(np.abs(off)) > MAX_OFFSET:
+                raise ValueError(f"offset must be finite and within +-{MAX_OFFSET:g}")
+            self.offset = np.ascontiguousarray(off)
+        excl = np.asarray([] if excluded is None else excluded, dtype=np.int64).ravel()
+        if excl.size and (excl.min() < 0 or excl.max() >= p):
+            raise ValueError(f"excluded must index the {p} columns of X")
+        self.excluded = np.ascontiguousarray(excl, dtype=np.int32)
+        starts = np.concatenate([[0], np.cumsum([part.forest_idx.shape[0] for part in parts])]).astype(np.int64)
+        total = int(starts[-1])
+        if draws is None:
+            idx = np.arange(total, dtype=np.int64)
+        else:
+            idx = np.asarray(draws, dtype=np.int64).ravel()
+            if idx.size and (idx.min() < 0 or idx.max() >= total):
+                raise ValueError(f"draws must index the {total} stored draws")
+        self.D = D = int(idx.size)
+        self.hdi_prob = hdi_prob
+        self.q, self.hdi_k, self.code = _spec(D, quantiles, hdi_prob, transform)
+        from .trees import pooled_history
+
+        cached = getattr(sampler, "pooled_history", None)  # (the multi-chain sampler keeps it)
+        self.pool, table = cached() if cached is not None else pooled_history(parts)
+        self.fidx = np.ascontiguousarray(np.asarray(table)[idx], dtype=np.int32)
+        self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None
+
+    def run(self, keep_matrix: bool = False):
+        """-> (the public dict, the predictions ``(D, K, n)`` or None).  ``keep_matrix``: also copy every block's
+        predictions to the host (partial dependence returns them next to their summary)."""
+        from .sampler import default_backend
+
+        be = _hip(self.backend() if self.backend is not None else default_backend())
+        lib, mem = be.lib, be.mem
+        n, D, K, p, Q = self.n, self.D, self.K, self.p, self.q.size
+        per_row = 8 * (p + K * (D + 1 + 2 + Q + 2))
+        block = max(64, min(n, _block_bytes() // per_row // 64 * 64))
+        stats = np.empty((2 + Q + 2, K, n))
+        pred = np.empty((D, K, n)) if keep_matrix else None
+        carr = self.pool.as_c()
+        excl = self.excluded
+        for r0 in range(0, n, block):
+            r1 = min(n, r0 + block)
+            nb = r1 - r0
+            xd = mem.from_host(self.X[r0:r1])
+            od = None if self.offset is None else mem.from_host(np.ascontiguousarray(self.offset[:, r0:r1]))
+            md = mem.empty((D * K * nb,), np.float64)  # [D][K][nb]: K * nb columns over the draws
+            rc = lib.lib.pgb_predict(C.byref(carr), self.fidx.ctypes.data, D, self.m, mem.ptr(xd), nb, p, p,
+                                     excl.ctypes.data if excl.size else None, int(excl.size), mem.ptr(md), mem.stream_ptr)
+            lib.check(rc, "pgb_predict")
+            stats[:, :, r0:r1] = _summary_block(lib, mem, md, D, K * nb, K * nb, od, self.code, self.q,
+                                                self.hdi_k).reshape(-1, K, nb)
+            if keep_matrix:
+                pred[:, :, r0:r1] = mem.to_host(md).reshape(D, K, nb)
+        return _result(stats, n, K, self.q, self.hdi_prob, self.hdi_k, D), pred
+
+
+def posterior_summary(sampler, X, draws=None, quantiles=DEFAULT_QUANTILES, hdi_prob=DEFAULT_HDI_PROB,
+                      transform: str = "identity", offset=None, excluded=None) -> dict:
+    """Per-row summaries over the posterior draws of the BART function at the rows of ``X``, computed on the device.
+
+    ``sampler``: what ``_get_posterior_sampler(op)`` or ``PosteriorSampler.from_history`` returns (several chains are
+    summarised as one pool).  ``draws``: indexes of the stored draws (default: all; between 2 and 16384).
+    ``quantiles``: up to 16 levels in [0, 1] (NumPy's default linear interpolation).  ``hdi_prob``: the mass of the
+    highest-density interval (``importance.hdi``; ``None``: no interval).  ``transform``: ``"identity"``, ``"exp"``,
+    ``"logistic"`` or ``"probit"`` (the normal CDF), applied to every prediction -- after ``offset`` ``(K, n_rows)``
+    has been added -- before anything is summarised.  ``excluded``: covariates marginalised out by the trees' own
+    counts, as in ``sample_posterior``.
+
+    Returns ``mean``, ``sd``, ``var`` (ddof 1), each ``(n_rows, K)``; ``quantiles`` ``(Q, n_rows, K)``; ``hdi``
+    ``(2, n_rows, K)`` (``None`` without ``hdi_prob``); and ``q``, ``hdi_prob``, ``n_draws``.  Rows are processed in
+    blocks of at most ``PGB_PW_BLOCK_BYTES`` of device scratch; results do not depend on the blocking, nor on the
+    order of the draws."""
+    return _Job(sampler, X, draws, quantiles, hdi_prob, transform, offset, excluded).run()[0]
+
+
+def summarize_matrix(a, quantiles=DEFAULT_QUANTILES, hdi_prob=DEFAULT_HDI_PROB, transform: str = "identity",
+                     backend=None) -> dict:
+    """:func:`posterior_summary`'s numbers for a matrix ``a`` ``(D, n)`` of draws held on the host (uploaded in blocks
+    of columns of at most ``PGB_PW_BLOCK_BYTES``): arrays ``(n,)``, ``quantiles`` ``(Q, n)``, ``hdi`` ``(2, n)``."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError(f"a must be a matrix (draws, columns), got shape {a.shape}")
+    D, n = int(a.shape[0]), int(a.shape[1])
+    q, hdi_k, code = _spec(D, quantiles, hdi_prob, transform)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("a must be finite")
+    be = _hip(backend)
+    lib, mem = be.lib, be.mem
+    block = max(64, min(n, _block_bytes() // (8 * (D + 4 + q.size)) // 64 * 64))
+    stats = np.empty((2 + q.size + 2, n))
+    for r0 in range(0, n, block):
+        r1 = min(n, r0 + block)
+        md = mem.from_host(np.ascontiguousarray(a[:, r0:r1]))
+        stats[:, r0:r1] = _summary_block(lib, mem, md, D, r1 - r0, r1 - r0, None, code, q, hdi_k)
+    res = _result(stats, n, 1, q, hdi_prob, hdi_k, D)
+    for key in ("mean", "sd", "var", "quantiles", "hdi"):
+        if res[key] is not None:
+            res[key] = res[key][..., 0]
+    return res

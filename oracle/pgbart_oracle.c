@@ -1057,25 +1057,62 @@ static void o_predict_rec(const pgb_tree_arrays* T, int base, int k, const doubl
   }
 }
 
-/* A malformed history (truncated file, mismatched m) must be an error, not an out-of-bounds walk:
+/* A malformed history (truncated file, mismatched m, hand-built arrays) must be an error, not an out-of-bounds walk
+ * and not a recursion that never ends:
  * 1 = forest index outside the tree list, 2 = inconsistent node arrays, 3 = split column >= p,
- * 4 = unknown split rule on a node. */
+ * 4 = unknown split rule on a node, 5 = the nodes reachable from node 0 do not form a tree rooted there (a node is
+ * its own child or ancestor, has two parents, or the root is a child), 6 = a node deeper than PGB_MAX_DEPTH (the
+ * root has depth 0; the product's walk keeps one stack entry per marginalised level), -1 = out of memory.
+ * The checks and their order are the product's (pred_validate, pgb_host.h): breadth-first from node 0, left before
+ * right, tree by tree after that tree's range checks.  Unreachable nodes are never walked and are left alone. */
 static int pgb_validate_forest(const pgb_tree_arrays* T, const int32_t* fidx, int32_t n_forests, int32_t m,
                                int32_t p) {
   for (int64_t i = 0; i < (int64_t)n_forests * m; ++i)
     if (fidx[i] < 0 || fidx[i] >= T->n_trees) return 1;
   if (T->n_trees < 0 || T->total_nodes < 0) return 2;
+  int32_t* buf = NULL;
+  int cap = 0;
   for (int t = 0; t < T->n_trees; ++t) {
     const int base = T->node_off[t], end = T->node_off[t + 1];
-    if (base < 0 || end <= base || end > T->total_nodes) return 2;
+    if (base < 0 || end <= base || end > T->total_nodes) { free(buf); return 2; }
     for (int g = base; g < end; ++g) {
       if (T->var[g] < 0) continue;
-      if (T->var[g] >= p) return 3;
-      if (T->rule && T->rule[g] != PGB_RULE_CONTINUOUS && T->rule[g] != PGB_RULE_ONEHOT && T->rule[g] != PGB_RULE_SUBSET)
+      if (T->var[g] >= p) { free(buf); return 3; }
+      if (T->rule && T->rule[g] != PGB_RULE_CONTINUOUS && T->rule[g] != PGB_RULE_ONEHOT && T->rule[g] != PGB_RULE_SUBSET) {
+        free(buf);
         return 4;
-      if (T->left[g] < 0 || T->right[g] < 0 || T->left[g] >= end - base || T->right[g] >= end - base) return 2;
+      }
+      if (T->left[g] < 0 || T->right[g] < 0 || T->left[g] >= end - base || T->right[g] >= end - base) {
+        free(buf);
+        return 2;
+      }
+    }
+    const int nn = end - base;
+    if (nn > cap) {
+      int32_t* nb = (int32_t*)realloc(buf, (size_t)nn * 2 * sizeof(int32_t));
+      if (!nb) { free(buf); return -1; }
+      buf = nb;
+      cap = nn;
+    }
+    int32_t* dep = buf;       /* depth of every node reached from the root, -1: not reached */
+    int32_t* todo = buf + nn; /* the nodes to visit */
+    for (int k = 0; k < nn; ++k) dep[k] = -1;
+    int n_todo = 1;
+    dep[0] = 0;
+    todo[0] = 0;
+    for (int q = 0; q < n_todo; ++q) {
+      const int k = todo[q];
+      if (T->var[base + k] < 0) continue;
+      const int32_t ch[2] = {T->left[base + k], T->right[base + k]};
+      for (int s = 0; s < 2; ++s) {
+        if (dep[ch[s]] >= 0) { free(buf); return 5; }
+        dep[ch[s]] = dep[k] + 1;
+        if (dep[ch[s]] > PGB_MAX_DEPTH) { free(buf); return 6; }
+        todo[n_todo++] = ch[s];
+      }
     }
   }
+  free(buf);
   return 0;
 }
 
@@ -1084,6 +1121,7 @@ int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, in
                 const int32_t* excluded, int32_t n_excluded, double* out, void* stream) {
   (void)stream;
   if (!trees || !forest_tree_idx || !X || !out) return fail(PGB_E_INVALID, "null argument");
+  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict: ldx must be >= p");
   int K = trees->n_outputs;
   {
     int vrc = pgb_validate_forest(trees, forest_tree_idx, n_forests, m, p);
@@ -1091,6 +1129,10 @@ int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, in
     if (vrc == 2) return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
     if (vrc == 3) return fail(PGB_E_INVALID, "a tree splits on a column X does not have");
     if (vrc == 4) return fail(PGB_E_INVALID, "a split node carries an unknown split rule");
+    if (vrc == 5)
+      return fail(PGB_E_INVALID, "a tree's nodes do not form a tree rooted at node 0 (a node is its own ancestor or has two parents)");
+    if (vrc == 6) return fail(PGB_E_INVALID, "a tree is deeper than PGB_MAX_DEPTH = " PGB_STR(PGB_MAX_DEPTH));
+    if (vrc < 0) return fail(PGB_E_NOMEM, "out of memory");
   }
   uint8_t* excl = (uint8_t*)calloc(p, 1);
   for (int e = 0; e < n_excluded; ++e)

@@ -1437,8 +1437,19 @@ extern "C" int pgb_get_split_weights(pgb_handle* h, double* out) {
   return PGB_OK;
 }
 
-// The history of a prediction (pgb_predict, pgb_pointwise_loglik), checked: a malformed one (truncated file,
-// mismatched m) is an error, not an out-of-bounds walk.
+// The history of a prediction (pgb_predict, pgb_pointwise_loglik, pgb_predict_ice), checked: a malformed one
+// (truncated file, mismatched m, hand-built arrays) is an error, not an out-of-bounds walk and not a walk that never
+// ends.  Beyond the ranges of the indices, every tree must be WALKABLE ("Walkable histories"):
+//   * the nodes reachable from node 0 form a tree rooted there: no node is its own child or ancestor, none has two
+//     parents, and the root is nobody's child -- the general walk of pgb_pred_walk.h follows left / right until it
+//     meets a leaf, so a cycle would keep a wave on the device for ever;
+//   * no node lies deeper than PGB_MAX_DEPTH (the root has depth 0) -- a walk that marginalises pushes one entry per
+//     level on a private stack of PGB_MAX_DEPTH + 2 entries.  Both samplers stop splitting at that depth
+//     (prior_leaf), so only loaded or hand-built arrays can break the rule.
+// Nodes that cannot be reached from the root are never walked and are left alone.  The oracle's pgb_validate_forest
+// makes the same checks in the same order and pgb_predict reports them with the same messages.
+#define PGB_MSG_NOT_A_TREE "a tree's nodes do not form a tree rooted at node 0 (a node is its own ancestor or has two parents)"
+#define PGB_MSG_TOO_DEEP "a tree is deeper than PGB_MAX_DEPTH = " PGB_STR(PGB_MAX_DEPTH)
 static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
                          int32_t p) {
   if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
@@ -1447,6 +1458,7 @@ static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tre
   for (long long i = 0; i < (long long)n_forests * m; ++i)
     if (forest_tree_idx[i] < 0 || forest_tree_idx[i] >= trees->n_trees)
       return fail(PGB_E_INVALID, "forest_tree_idx entry outside [0, n_trees)");
+  std::vector<int32_t> dep, todo;  // depth of every node reached from the root (-1: not reached), the nodes to visit
   for (int t = 0; t < trees->n_trees; ++t) {
     const int base = trees->node_off[t], end = trees->node_off[t + 1];
     if (base < 0 || end <= base || end > trees->total_nodes)
@@ -1459,6 +1471,24 @@ static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tre
         return fail(PGB_E_INVALID, "a split node carries an unknown split rule");
       if (trees->left[g] < 0 || trees->right[g] < 0 || trees->left[g] >= end - base || trees->right[g] >= end - base)
         return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
+    }
+    // walkable: breadth-first from node 0, left before right; a child met twice (or the root met at all) is a
+    // second parent or a cycle
+    const int nn = end - base;
+    dep.assign((size_t)nn, -1);
+    todo.clear();
+    dep[0] = 0;
+    todo.push_back(0);
+    for (size_t q = 0; q < todo.size(); ++q) {
+      const int k = todo[q];
+      if (trees->var[base + k] < 0) continue;
+      const int32_t ch[2] = {trees->left[base + k], trees->right[base + k]};
+      for (int s = 0; s < 2; ++s) {
+        if (dep[ch[s]] >= 0) return fail(PGB_E_INVALID, PGB_MSG_NOT_A_TREE);
+        dep[ch[s]] = dep[k] + 1;
+        if (dep[ch[s]] > PGB_MAX_DEPTH) return fail(PGB_E_INVALID, PGB_MSG_TOO_DEEP);
+        todo.push_back(ch[s]);
+      }
     }
   }
   return PGB_OK;
@@ -1603,6 +1633,7 @@ extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_t
                            const int32_t* excluded_host, int32_t n_excluded,
                            double* out_dev, void* stream) {
   if (!trees || !forest_tree_idx || !X_dev || !out_dev) return fail(PGB_E_INVALID, "null argument");
+  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict: ldx must be >= p");  // (rows that overlap: never a layout)
   if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
   if (n_forests < 1 || n_rows < 1) return PGB_OK;
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);

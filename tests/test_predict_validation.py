@@ -1,0 +1,189 @@
+"""Histories that cannot be walked are refused before anything touches a device (``pred_validate`` in
+``pgb_host.h``, ``pgb_validate_forest`` in the oracle): a tree whose nodes do not form a tree rooted at node 0 would
+keep the general walk of ``pgb_pred_walk.h`` going for ever, one deeper than ``PGB_MAX_DEPTH`` would overrun its stack.
+
+Every check precedes the first HIP call, so the library answers without a GPU; host buffers stand in for device memory
+and are never dereferenced.  None of these pools is ever passed to a launch."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import _predict_exact as E
+from _oracle import oracle_backend
+from pymc_bart_amd import _abi
+
+E_INVALID = -1
+MAX_DEPTH = 64  # PGB_MAX_DEPTH (include/pgbart_spec.h)
+NOT_A_TREE = "a tree's nodes do not form a tree rooted at node 0 (a node is its own ancestor or has two parents)"
+TOO_DEEP = f"a tree is deeper than PGB_MAX_DEPTH = {MAX_DEPTH}"
+VALIDATION_WORDS = ("rooted at node 0", "deeper than", "inconsistent", "forest_tree_idx", "column X does not have",
+                    "split rule", "ldx")
+P = 3
+
+
+def _split_q(rng, j):
+    return E.dyadic(rng, 2, 2.0)
+
+
+def _good_pool(extra=()):
+    """A stump, a depth-3 tree (7 splits, nodes 0 .. 14 breadth first) and whatever ``extra`` adds."""
+    rng = np.random.default_rng(5)
+    return E.build_pool([E.dyadic_leaf(rng, 1), E.complete_tree(rng, 1, 3, [0, 1, 2], _split_q)] + list(extra), 1)
+
+
+def _chain(depth, side="left"):
+    return E.chain_tree(np.random.default_rng(depth), 1, depth, [0, 1, 2], _split_q, side)
+
+
+def _malformed():
+    """name -> (pool, the message).  Tree 1 starts at pool node 1; its local nodes 1 and 2 are the root's children."""
+    out = {}
+    pool = _good_pool()
+    pool.left[1 + 1] = 1                                      # node 1 is its own left child
+    out["self-loop"] = (pool, NOT_A_TREE)
+    pool = _good_pool()
+    pool.left[1 + 3] = 1                                      # node 1 -> node 3 -> node 1
+    out["2-cycle"] = (pool, NOT_A_TREE)
+    pool = _good_pool()
+    pool.right[1 + 2] = 0                                     # the root as a child
+    out["root as a child"] = (pool, NOT_A_TREE)
+    pool = _good_pool()
+    pool.left[1 + 2] = 3                                      # node 3 under node 1 and under node 2
+    out["shared child"] = (pool, NOT_A_TREE)
+    pool = _good_pool()
+    pool.right[1 + 1] = pool.left[1 + 1]                      # both children of node 1 are the same node
+    out["one node as both children"] = (pool, NOT_A_TREE)
+    for extra in (1, 3):
+        for side in ("left", "right"):
+            out[f"depth {MAX_DEPTH} + {extra}, {side}"] = (_good_pool([_chain(MAX_DEPTH + extra, side)]), TOO_DEEP)
+    return out
+
+
+class Calls:
+    """The three entry points of the HIP library and ``pgb_predict`` of the oracle on one pool; every pointer to
+    "device" memory is a host buffer."""
+
+    def __init__(self, hip_lib, oracle):
+        self.hip, self.oracle = hip_lib, oracle.lib
+        self.buf = np.zeros(256)
+
+    def run(self, pool, ldx=P, compiled=False):
+        fidx = np.arange(pool.n_trees, dtype=np.int32)[None, :].copy()
+        D, m = fidx.shape
+        carr = pool.as_c()
+        b = self.buf.ctypes.data
+        out = {}
+        for name, lib in (("pgb_predict", self.hip), ("oracle pgb_predict", self.oracle)):
+            if compiled:
+                continue
+            rc = lib.lib.pgb_predict(C.byref(carr), fidx.ctypes.data, D, m, b, 4, P, ldx, None, 0, b, None)
+            out[name] = (rc, lib.lib.pgb_last_error().decode())
+        sigma = np.ones(D)
+        lik = _abi.PointwiseLik()
+        lik.family, lik.n_params, lik.params_host, lik.y_dev = _abi.FAMILIES["normal"], 1, sigma.ctypes.data, b
+        if compiled:                                          # (no code object: refused right after the history)
+            lik.family, lik.n_params, lik.params_host = _abi.FAMILIES["compiled"], 0, None
+        nc = C.c_int64(0)
+        rc = self.hip.pointwise_entry_point()(C.byref(carr), fidx.ctypes.data, D, m, b, 4, P, ldx, C.byref(lik), b, None,
+                                              C.byref(nc), None)
+        out["pgb_pointwise_loglik"] = (rc, self.hip.lib.pgb_last_error().decode())
+        if compiled:
+            return out
+        cols = np.array([1], np.int32)
+        picks = np.zeros((1, 2, 3), np.int32)
+        rc = self.hip.ice_entry_point()(C.byref(carr), fidx.ctypes.data, D, m, b, 4, P, ldx, b, 2, P, cols.ctypes.data, 1,
+                                        picks.ctypes.data, 3, b, None)
+        out["pgb_predict_ice"] = (rc, self.hip.lib.pgb_last_error().decode())
+        return out
+
+
+@pytest.fixture(scope="module")
+def calls():
+    if not os.path.exists(_abi.hip_library_path()):
+        pytest.skip("libpgbart_hip.so has not been built")
+    return Calls(_abi.load_hip_library(), oracle_backend())
+
+
+@pytest.mark.parametrize("name", list(_malformed()))
+def test_a_history_that_cannot_be_walked_is_refused_by_every_entry_point(name, calls):
+    pool, message = _malformed()[name]
+    got = calls.run(pool)
+    assert set(got) == {"pgb_predict", "oracle pgb_predict", "pgb_pointwise_loglik", "pgb_predict_ice"}
+    for entry, (rc, msg) in got.items():
+        assert rc == E_INVALID and msg == message, (name, entry, rc, msg)
+
+
+def test_every_entry_point_refuses_rows_that_overlap(calls):
+    got = calls.run(_good_pool(), ldx=P - 1)
+    for entry, (rc, msg) in got.items():
+        assert rc == E_INVALID and "ldx" in msg, (entry, rc, msg)
+    assert got["pgb_predict"][1] == got["oracle pgb_predict"][1] == "pgb_predict: ldx must be >= p"
+
+
+def test_the_range_checks_still_answer_first(calls):
+    """An index outside the tree precedes the graph check (which would read beyond the tree's nodes)."""
+    pool = _good_pool()
+    pool.left[1 + 1] = 15
+    for entry, (rc, msg) in calls.run(pool).items():
+        assert rc == E_INVALID and "tree arrays are inconsistent" in msg, (entry, msg)
+
+
+def test_nodes_that_cannot_be_reached_are_left_alone_and_the_deepest_chain_passes(calls):
+    """A chain of exactly PGB_MAX_DEPTH levels, next to a tree with a cycle among nodes its root never reaches: the
+    oracle predicts them; the library's history check lets them through -- shown by the refusal that FOLLOWS it in
+    pgb_pointwise_loglik (a compiled family without a code object), which needs no device and launches nothing."""
+    rng = np.random.default_rng(9)
+    detached = E.build_pool([E.Split(0, 0.5, E.dyadic_leaf(rng, 1), E.dyadic_leaf(rng, 1))], 1)
+    arrays = {f: np.concatenate([getattr(detached, f), getattr(detached, f)[:1]]) for f in
+              ("var", "split", "left", "right", "count", "svar", "xbar", "rule")}
+    arrays["left"][3] = arrays["right"][3] = 3                # node 3: a self-loop nobody points at
+    from pymc_bart_amd.trees import TreeArrays
+    island = TreeArrays(n_outputs=1, tree_id=np.zeros(1, np.int32), node_off=np.array([0, 4], np.int32),
+                        value=np.concatenate([detached.value, detached.value[:1]]),
+                        slope=np.concatenate([detached.slope, detached.slope[:1]]), **arrays)
+    pool = TreeArrays.concat([_good_pool([_chain(MAX_DEPTH, "left"), _chain(MAX_DEPTH, "right")]), island])
+    assert [E.tree_depth(pool, t) for t in range(pool.n_trees)] == [0, 3, MAX_DEPTH, MAX_DEPTH, 1]
+    got = calls.run(pool, compiled=True)
+    rc, msg = got["pgb_pointwise_loglik"]
+    assert rc == E_INVALID and msg == "the compiled family needs a code object", msg
+    assert not any(w in msg for w in VALIDATION_WORDS)
+    # the oracle runs on the host: it walks the pool, and gives what the exact reference gives
+    ora = oracle_backend()
+    fidx = np.arange(pool.n_trees, dtype=np.int32)[None, :].copy()
+    X = E.dyadic(rng, 4, 2.5, (9, P))
+    out = np.zeros(9)
+    carr = pool.as_c()
+    rc = ora.lib.lib.pgb_predict(C.byref(carr), fidx.ctypes.data, 1, pool.n_trees, X.ctypes.data, 9, P, P, None, 0,
+                                 out.ctypes.data, None)
+    assert rc == 0, ora.lib.lib.pgb_last_error().decode()
+    assert np.array_equal(out, E.walk(pool, fidx, X).exact_class()[0, 0])
+
+
+def test_sampler_built_trees_respect_the_depth_bound(oracle):
+    """Both samplers stop splitting at depth PGB_MAX_DEPTH (a node there is a leaf with probability 1), so the check
+    refuses nothing they produce: even a prior that never stops a split on its own."""
+    from pymc_bart_amd.sampler import PyBartSettings, PySampler
+
+    rng = np.random.default_rng(2)
+    n, p = 400, 2
+    X = rng.uniform(0, 1, (n, p))
+    Y = np.sin(40 * X[:, 0]) + rng.normal(0, 0.1, n)
+    st = PyBartSettings.from_data(X, Y, m=2, num_particles=4, seed=11)
+    for d in range(MAX_DEPTH):
+        st.prior_leaf[d] = 0.0
+    s = PySampler(st, X, Y, np.zeros(p, np.int32), np.ones(p), backend=oracle)
+    deepest = 0
+    for it in range(6):
+        s.set_likelihood([0.1])
+        s.step(True)
+        trees = s.export_trees(1)
+        deepest = max([deepest] + [E.tree_depth(trees, t) for t in range(trees.n_trees)])
+        fidx = np.arange(trees.n_trees, dtype=np.int32)[None, :].copy()
+        out = np.zeros(n)
+        carr = trees.as_c()
+        rc = oracle.lib.lib.pgb_predict(C.byref(carr), fidx.ctypes.data, 1, trees.n_trees, X.ctypes.data, n, p, p, None,
+                                        0, out.ctypes.data, None)
+        assert rc == 0, oracle.lib.lib.pgb_last_error().decode()
+    assert 1 <= deepest <= MAX_DEPTH

@@ -41,6 +41,7 @@
 #include "pgbart_spec.h"
 
 #define PGB_IMAGE_VERSION 1
+#define PGB_IMAGE_COUNT_MAX ((int64_t)1 << 62) /* counters and cursors of an image: far from where adding to them overflows */
 
 typedef struct {
   char magic[8];        /* "PGBIMAGE"                                                        */
@@ -128,8 +129,77 @@ static inline void pgb_image_begin(void* buf, int64_t bytes, const pgb_settings*
   if (((int64_t)s->m * s->n) & 7) memset(v.lid + (((int64_t)s->m * s->n) & ~(int64_t)7), 0, 8);
 }
 
+static inline int pgb_image_finite(const double* a, int64_t cnt) {
+  for (int64_t i = 0; i < cnt; ++i)
+    if (!(a[i] - a[i] == 0.0)) return 0;
+  return 1;
+}
+
+/* The second half of pgb_image_check, on a record whose offsets and indices are already known to stay inside it:
+ * is the CONTENT a chain some writer could have produced?  Every tree is one tree (a root at depth 0, every other
+ * node with exactly one parent one level up), the row labels of a tree name its leaves (or PGB_ORPHAN) and count
+ * what the leaves say they hold, and no number a later step computes with is non-finite.  (The count of an INNER
+ * node is only held to [0, n]: rows with a missing split value leave the tree there, so it need not be the sum of
+ * its children's.)  The label scan is one pass over the m n bytes with a 256-bin histogram per tree. */
+static inline const char* pgb_image_check_content(const pgb_image_header* hd, const pgb_image_view* v) {
+  const int64_t n = hd->s.n;
+  const int32_t m = hd->s.m, p = hd->s.p, K = hd->s.n_outputs, N = hd->total_nodes;
+  for (int32_t k = 0; k < K; ++k)
+    if (!(hd->leaf_sd[k] - hd->leaf_sd[k] == 0.0) || !(hd->leaf_sd[k] > 0.0)) return "checkpoint is inconsistent (leaf_sd)";
+  if (!pgb_image_finite(hd->lik_param, 2)) return "checkpoint is inconsistent (likelihood parameters)";
+  if (!pgb_image_finite(v->sum_trees, (int64_t)K * n)) return "checkpoint is inconsistent (sum_trees is not finite)";
+  if (!pgb_image_finite(v->rs_mean, (int64_t)K * n) || !pgb_image_finite(v->rs_m2, (int64_t)K * n))
+    return "checkpoint is inconsistent (running sd is not finite)";
+  int64_t alpha_sum = 0;
+  for (int32_t j = 0; j < p; ++j) {
+    if (v->alpha[j] < 0) return "checkpoint is inconsistent (negative split weight)";
+    if (v->cdf[j] < (j ? v->cdf[j - 1] : 0)) return "checkpoint is inconsistent (split weight sums decrease)";
+    if (v->alpha[j] > PGB_IMAGE_COUNT_MAX - alpha_sum || v->cdf[j] > PGB_IMAGE_COUNT_MAX)
+      return "checkpoint is inconsistent (split weights beyond 2^62)"; /* (their prefix sums are int64) */
+    alpha_sum += v->alpha[j];
+  }
+  if (!pgb_image_finite(v->value, (int64_t)N * K) || !pgb_image_finite(v->slope, (int64_t)N * K) ||
+      !pgb_image_finite(v->xbar, N))
+    return "checkpoint is inconsistent (leaf values are not finite)";
+  for (int32_t t = 0; t < m; ++t) {
+    const int32_t base = v->node_off[t], nn = v->node_off[t + 1] - base;
+    uint8_t parents[PGB_MAX_NODES];
+    uint8_t is_leaf_label[256];
+    int64_t hist[256];
+    memset(parents, 0, sizeof parents);
+    memset(is_leaf_label, 0, sizeof is_leaf_label);
+    memset(hist, 0, sizeof hist);
+    const uint8_t* lid = v->lid + (int64_t)t * n;
+    for (int64_t i = 0; i < n; ++i) hist[lid[i]] += 1;
+    if (v->depth[base] != 0) return "checkpoint is inconsistent (root depth)";
+    for (int32_t k = 0; k < nn; ++k) {
+      const int32_t g = base + k;
+      if (v->count[g] < 0 || v->count[g] > n) return "checkpoint is inconsistent (row count)";
+      if (k > 0 && parents[k] != 1) return "checkpoint is inconsistent (a node without a parent, or with two)";
+      if (v->var[g] >= 0) {
+        const int32_t l = v->left[g], r = v->right[g];
+        if (l == r) return "checkpoint is inconsistent (children)";
+        if (!(v->split[g] - v->split[g] == 0.0)) return "checkpoint is inconsistent (split value is not finite)";
+        if (v->depth[base + l] != v->depth[g] + 1 || v->depth[base + r] != v->depth[g] + 1)
+          return "checkpoint is inconsistent (depth)";
+        if (parents[l] < 2) parents[l] += 1; /* (children lie after their parent: judged when the walk gets there) */
+        if (parents[r] < 2) parents[r] += 1;
+      } else {
+        const int32_t lb = v->label[g];
+        if (is_leaf_label[lb]) return "checkpoint is inconsistent (a leaf label used twice)";
+        is_leaf_label[lb] = 1;
+        if (v->count[g] != hist[lb]) return "checkpoint is inconsistent (leaf count differs from its rows)";
+      }
+    }
+    for (int32_t b = 0; b < PGB_ORPHAN; ++b)
+      if (hist[b] && !is_leaf_label[b]) return "checkpoint is inconsistent (row label of no leaf)";
+  }
+  return (const char*)0;
+}
+
 /* Is `buf` an image this sampler can continue?  Returns NULL when it is, else what is wrong (a static string).
- * Checks everything a loader indexes by: a truncated or foreign record is an error, never an out-of-bounds walk. */
+ * First everything a loader indexes by: a truncated or foreign record is an error, never an out-of-bounds walk;
+ * then the content (pgb_image_check_content): an edited or damaged record is an error, never another chain. */
 static inline const char* pgb_image_check(const void* buf, int64_t bytes, const pgb_settings* mine) {
   if (bytes < (int64_t)sizeof(pgb_image_header)) return "checkpoint truncated";
   pgb_image_header hd;
@@ -141,15 +211,22 @@ static inline const char* pgb_image_check(const void* buf, int64_t bytes, const 
   const int32_t m = hd.s.m, p = hd.s.p, K = hd.s.n_outputs, N = hd.total_nodes;
   if (N < m || (int64_t)N > (int64_t)m * PGB_MAX_NODES) return "checkpoint is inconsistent (node count)";
   if (hd.total_bytes != pgb_image_bytes(hd.s.n, p, m, K, N) || bytes < hd.total_bytes) return "checkpoint truncated";
-  if (hd.lower < 0 || hd.lower >= m || hd.last_lower < 0 || hd.last_n < 0 || hd.last_lower + hd.last_n > m ||
-      hd.iter < 0 || hd.rs_count < 0)
-    return "checkpoint is inconsistent (cursor)";
+  if (hd.lower < 0 || hd.lower >= m || hd.last_lower < 0 || hd.last_n < 0 || (int64_t)hd.last_lower + hd.last_n > m ||
+      hd.iter < 0 || hd.rs_count < 0 || hd.rs_count > hd.iter || hd.iter > PGB_IMAGE_COUNT_MAX)
+    return "checkpoint is inconsistent (cursor)"; /* (the running sd has seen the tuning updates: no more than all) */
+  {
+    const int64_t c[7] = {hd.ctr.particle_steps, hd.ctr.tree_updates, hd.ctr.rows_touched, hd.ctr.rounds,
+                          hd.ctr.saturations, hd.ctr.slots, hd.ctr.partitions};
+    for (int i = 0; i < 7; ++i)
+      if (c[i] < 0 || c[i] > PGB_IMAGE_COUNT_MAX) return "checkpoint is inconsistent (counters)";
+  }
   pgb_image_view v;
   pgb_image_bind((void*)buf, &hd, &v);
   if (v.node_off[0] != 0 || v.node_off[m] != N) return "checkpoint is inconsistent (node offsets)";
   for (int32_t t = 0; t < m; ++t) {
-    const int32_t base = v.node_off[t], nn = v.node_off[t + 1] - base;
-    if (nn < 1 || nn > PGB_MAX_NODES || base < 0 || base + nn > N) return "checkpoint is inconsistent (node offsets)";
+    const int64_t base64 = v.node_off[t], nn64 = (int64_t)v.node_off[t + 1] - base64; /* (any two int32: no overflow) */
+    if (nn64 < 1 || nn64 > PGB_MAX_NODES || base64 < 0 || base64 + nn64 > N) return "checkpoint is inconsistent (node offsets)";
+    const int32_t base = (int32_t)base64, nn = (int32_t)nn64;
     for (int32_t k = 0; k < nn; ++k) {
       const int32_t g = base + k;
       if (v.var[g] >= p) return "checkpoint is inconsistent (split column)";
@@ -162,7 +239,7 @@ static inline const char* pgb_image_check(const void* buf, int64_t bytes, const 
       if (v.depth[g] < 0 || v.depth[g] > PGB_MAX_NODES) return "checkpoint is inconsistent (depth)";
     }
   }
-  return (const char*)0;
+  return pgb_image_check_content(&hd, &v);
 }
 
 #endif /* PGBART_IMAGE_H */

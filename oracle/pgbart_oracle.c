@@ -270,6 +270,7 @@ int pgb_destroy(pgb_handle* h) {
 int pgb_set_data(pgb_handle* h, const double* X, int64_t ldx, const int32_t* rules,
                  const double* split_prior) {
   if (!h || !X || !rules || !split_prior) return fail(PGB_E_INVALID, "null argument");
+  h->have_data = 0; /* (a call that is refused below has already overwritten X and the rules: no data until one succeeds) */
   int64_t n = h->s.n;
   int p = h->s.p;
   if (ldx < p) return fail(PGB_E_INVALID, "ldx < p");

@@ -37,6 +37,11 @@ struct pgb_handle {
   int rows_grid;   // workgroups of the persistent row-pass grid (dispatch costs ~3.5 ns each)
   int ll_grid;     // ... of the log-likelihood pass
   int rows_mk_cap; // K-vector row pass: workgroups its instance keeps resident (0: not queried yet)
+  // 16-bit order keys: decided by pgb_set_data alone, for the data it was last given.  This one flag picks the KEYS
+  // instance of k_ctrl and the F32 instance of the row pass TOGETHER (they disagree on the stride of the chunk-count
+  // rows otherwise); d.XK16 is xk16_buf while it is set and null while it is not
+  int use_keys;
+  uint16_t* xk16_buf;  // [p][n_pad], allocated by the first pgb_set_data that wants keys, kept until pgb_destroy
   // the instance of k_loglik this sampler launches (family / outputs / response)
   void (*ll_kernel)(const Dev*, int, int, const Cmd*, const Ctrl*, const Job*, const Acc*, const InitAcc*);
   int sigma_dirty;
@@ -241,6 +246,8 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   h->has_subset = 0;
   h->rows_grid = 1024;
   h->rows_mk_cap = 0;
+  h->use_keys = 0;
+  h->xk16_buf = nullptr;
   h->prof_buf = nullptr;
   h->prof = 0;
   for (int k = 0; k < PK_COUNT; ++k) {
@@ -586,6 +593,7 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
   if (!h || !X_dev || !rules_host || !split_prior_host) return fail(PGB_E_INVALID, "null argument");
   JOIN_ASYNC(h);
   h->out_valid = 0;
+  h->have_data = 0;  // (a call that is refused below has already touched XT, the rules or the keys: no data until one succeeds)
   Dev& d = h->d;
   if (ldx < d.p) return fail(PGB_E_INVALID, "ldx < p");
   double mx = 0.0;
@@ -637,16 +645,21 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
     size_t min_bytes = (size_t)192 << 20;
     if (const char* e = getenv("PGB_X32_MIN_MB")) min_bytes = (size_t)atoll(e) << 20;
     const size_t count = (size_t)d.p * d.n_pad;
-    if (d.response == PGB_RESPONSE_CONSTANT && !h->has_subset && count * sizeof(double) >= min_bytes) {
-      if (!d.XK16) {
+    // THE predicate: keys are in use for this data or they are not -- whatever an earlier call decided
+    const int use_keys = d.response == PGB_RESPONSE_CONSTANT && !h->has_subset && count * sizeof(double) >= min_bytes;
+    if (use_keys != h->use_keys) h->rows_mk_cap = 0;  // (another instance of the K-vector row pass from here on)
+    h->use_keys = use_keys;
+    d.XK16 = nullptr;  // (the keys of an earlier matrix are ignored; the buffer stays for a later call that wants keys)
+    if (use_keys) {
+      if (!h->xk16_buf) {
         uint16_t* xk = nullptr;
         int rck = dalloc(h, &xk, count);
         if (rck != PGB_OK) return rck;
-        d.XK16 = xk;
-        h->rows_mk_cap = 0;  // (another instance of the K-vector row pass from here on)
+        h->xk16_buf = xk;
       }
-      hipError_t e = order_keys_build(d.XT, (long long)d.n, (long long)d.n_pad, d.p, (uint16_t*)d.XK16, sm);
+      hipError_t e = order_keys_build(d.XT, (long long)d.n, (long long)d.n_pad, d.p, h->xk16_buf, sm);
       if (e != hipSuccess) return fail_hip(e, "order keys of the design matrix");
+      d.XK16 = h->xk16_buf;
     }
   }
   double* prior_stage = nullptr;
@@ -798,6 +811,7 @@ static int prof_events(pgb_handle* h, int k, hipEvent_t* e0, hipEvent_t* e1) {
 static int enqueue_slots(pgb_handle* h, int count) {
   Dev& d = h->d;
   const bool lin = d.response != PGB_RESPONSE_CONSTANT;
+  const bool keys = h->use_keys != 0;  // KEYS of k_ctrl and F32 of the row pass: always chosen together (pgb_set_data)
   long long want = (long long)d.nchunks * (d.P - 1);
   if (want < d.n_pad / BT) want = d.n_pad / BT;
   if (want > h->rows_grid) want = h->rows_grid;
@@ -806,7 +820,7 @@ static int enqueue_slots(pgb_handle* h, int count) {
     // persistent grid larger than what stays resident leaves the surplus workgroups waiting for a first round of
     // items to finish (cfg5, in-kernel stamps: the last quarter of a 1024 grid started 22 us into a 27 us launch)
     if (h->rows_mk_cap == 0) {
-      const bool f32 = d.XK16 != nullptr;
+      const bool f32 = h->use_keys != 0;
       const void* kf = lin ? (const void*)k_rows_mk<0, true>
                        : d.K == 2 ? (f32 ? (const void*)k_rows_mk<2, false, true> : (const void*)k_rows_mk<2, false>)
                        : d.K == 3 ? (f32 ? (const void*)k_rows_mk<3, false, true> : (const void*)k_rows_mk<3, false>)
@@ -829,26 +843,26 @@ static int enqueue_slots(pgb_handle* h, int count) {
     int par = (int)(h->slot & 1);
 #define CTRL_ARGS(nwg) dd, par, (int)(nwg), d.ctrl, (const InitAcc*)d.initacc, (const Job*)d.jobs, (const Acc*)d.acc, (const DPart*)d.parts, (const uint16_t*)d.XK16
     if (d.K > 1 && lin) LAUNCH_K(PK_CTRL, (k_ctrl<true, true>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (d.K > 1 && d.XK16) LAUNCH_K(PK_CTRL, (k_ctrl<true, false, true>), gctrl, CTRL_ARGS(gctrl.x));
+    else if (d.K > 1 && keys) LAUNCH_K(PK_CTRL, (k_ctrl<true, false, true>), gctrl, CTRL_ARGS(gctrl.x));
     else if (d.K > 1) LAUNCH_K(PK_CTRL, (k_ctrl<true, false>), gctrl, CTRL_ARGS(gctrl.x));
     else if (lin) LAUNCH_K(PK_CTRL, (k_ctrl<false, true>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (d.XK16) LAUNCH_K(PK_CTRL, (k_ctrl<false, false, true>), dim3((unsigned)d.P), CTRL_ARGS(d.P));
+    else if (keys) LAUNCH_K(PK_CTRL, (k_ctrl<false, false, true>), dim3((unsigned)d.P), CTRL_ARGS(d.P));
     else LAUNCH_K(PK_CTRL, (k_ctrl<false, false>), dim3((unsigned)d.P), CTRL_ARGS(d.P));  // + the workgroup that builds the label tables ahead
 #undef CTRL_ARGS
 #define ROWS_ARGS dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs
     if (d.K > 1 && lin) {  // linear leaves: one instance for any K
       LAUNCH_K(PK_ROWS, (k_rows_mk<0, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     } else if (d.K == 2) {
-      if (d.XK16) LAUNCH_K(PK_ROWS, (k_rows_mk<2, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
+      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<2, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
       else LAUNCH_K(PK_ROWS, (k_rows_mk<2, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     } else if (d.K == 3) {
-      if (d.XK16) LAUNCH_K(PK_ROWS, (k_rows_mk<3, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
+      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<3, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
       else LAUNCH_K(PK_ROWS, (k_rows_mk<3, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     } else if (d.K == 4) {
-      if (d.XK16) LAUNCH_K(PK_ROWS, (k_rows_mk<4, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
+      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<4, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
       else LAUNCH_K(PK_ROWS, (k_rows_mk<4, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     } else if (d.K > 1) {
-      if (d.XK16) LAUNCH_K(PK_ROWS, (k_rows_mk<0, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
+      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<0, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
       else LAUNCH_K(PK_ROWS, (k_rows_mk<0, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     } else {
       const bool nrm = h->s.family == PGB_FAMILY_NORMAL;
@@ -861,7 +875,7 @@ static int enqueue_slots(pgb_handle* h, int count) {
       } else if (h->has_subset) {
         if (nrm) LAUNCH_K(PK_ROWS, (k_rows<true, true, false>), grows, ROWS_ARGS);
         else LAUNCH_K(PK_ROWS, (k_rows<true, false, false>), grows, ROWS_ARGS);
-      } else if (d.XK16 != nullptr) {  // 16-bit order keys of the split columns (matrix larger than the Infinity Cache)
+      } else if (keys) {  // 16-bit order keys of the split columns (matrix larger than the Infinity Cache)
         if (nrm) LAUNCH_K(PK_ROWS, (k_rows<false, true, false, true>), grows, ROWS_ARGS);
         else LAUNCH_K(PK_ROWS, (k_rows<false, false, false, true>), grows, ROWS_ARGS);
       } else {

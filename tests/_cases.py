@@ -451,3 +451,210 @@ def random_case(seed, large=False, compat=0):
     return dict(**extra, name=f"fuzz{seed}", compat=int(compat), response=response, X=X, Y=Y, m=m, P=P, steps=int(rng.integers(2, 5) if large else rng.integers(4, 14)), batch=batch, rules=rules,
                 prior=rng.uniform(0.5, 3.0, p), seed=int(rng.integers(0, 2**31)), family=fam, K=K,
                 alpha=float(rng.choice([0.95, 0.5, 0.999])), beta=float(rng.choice([2.0, 0.5, 1.0])))
+
+
+# ------------------------------------------------------------------ handle history (tests/test_handle_history*.py)
+# "A handle's history leaves no trace": after any sequence of setter calls, refused calls and loads the chain continues
+# bit for bit like a fresh handle given the same image and the same final inputs.
+
+HISTORY_STEPS = 12
+
+
+def make_history_case(kind, n=1025, P=10, rules="continuous", seed=0):
+    """The small model the history tests drive: n = 1025 rows (two chunks, a single row in the second), p = 5, m = 10
+    trees in batches of 3 (a tree lives through three changes of the inputs before it is rebuilt), 12 asteps, half of
+    them tuning.  `kind`: family, or family:K, with an optional /linear or /mix response."""
+    fam, _, response = kind.partition("/")
+    fam, _, K = fam.partition(":")
+    K = int(K) if K else 1
+    rng = np.random.default_rng(int(hashlib.sha1(f"history {kind} {n} {rules} {seed}".encode()).hexdigest()[:8], 16))
+    p = 5
+    X = rng.uniform(-2, 2, size=(n, p))
+    rl = np.zeros(p, np.int32)
+    prior = np.array([1.0, 1.0, 2.0, 2.0, 1.0])
+    if rules == "mixed":  # the rules of linear_mixed_rules: one-hot, subset (9 categories), subset with a single category
+        X[:, 2] = rng.integers(0, 3, n)
+        X[:, 3] = rng.integers(0, 9, n)
+        X[:, 4] = 1.0
+        X[rng.random(n) < 0.1, 3] = np.nan
+        rl = np.array([0, 0, 1, 2, 2], np.int32)
+    X[rng.random(n) < 0.1, 1] = np.nan
+    f = np.where(X[:, 0] < 0, 1.2 * X[:, 0] + 0.5, -0.8 * X[:, 0] + 0.5) + 0.4 * (X[:, 2] > 0)
+    c = dict(name=f"history/{kind}", X=X, m=10, P=P, steps=HISTORY_STEPS, batch=(3, 3), rules=rl, prior=prior, seed=2718 + seed,
+             family=fam, K=K, response=response or "constant", lik=lambda r: [])
+    if fam == "normal":
+        Y = f + rng.normal(0, 0.3, n)
+        c.update(lik=lambda r: [float(0.5 + r.random())])
+    elif fam in ("bernoulli_probit", "bernoulli_logit"):
+        Y = (rng.random(n) < 1 / (1 + np.exp(-1.5 * f))).astype(float)
+    elif fam in ("poisson_log", "negbin_log"):
+        Y = rng.poisson(np.exp(f)).astype(float)
+        c.update(bart_Y=np.log(Y + 0.5))
+        if fam == "negbin_log":
+            c.update(lik=lambda r: [float(r.uniform(1.0, 4.0))])
+    elif fam == "gamma_log":
+        Y = rng.gamma(3.0, np.exp(f) / 3.0) + 1e-6
+        c.update(bart_Y=np.log(Y), lik=lambda r: [float(r.uniform(1.0, 4.0))])
+    elif fam == "asymmetric_laplace":
+        Y = f + rng.normal(0, 0.3, n)
+        c.update(lik=lambda r: [float(r.uniform(0.2, 0.5)), float(r.uniform(0.2, 0.9))])
+    elif fam == "student_t":
+        Y = f + 0.2 * rng.standard_t(3, n)
+        c.update(lik=lambda r: [float(r.uniform(0.15, 0.4)), float(r.uniform(2.0, 8.0))])
+    elif fam == "categorical":
+        logits = np.stack([f * (k - 0.5 * (K - 1)) for k in range(K)]) + rng.gumbel(size=(K, n))
+        Y = np.argmax(logits, axis=0).astype(float)
+    elif fam == "normal_meanscale":
+        Y = f + rng.normal(0, 1, n) * (0.5 + (X[:, 0] > 0))
+    else:
+        raise KeyError(kind)
+    c.update(Y=Y)
+    return c
+
+
+def moving_inputs(c, swap=False, none_at=4, zero_at=8):
+    """The schedule of a model whose other terms move at every astep, as PGBART.astep drives the handle: a Normal
+    model gets `set_response(y - o_t)` and a moving sigma, a per-row family `set_offset(o_t)` ([K][n] for K-vector
+    leaves) and moving parameters.  One step inside the run resets the offset (`None`), another sets an all-zero
+    array (`swap` exchanges the two): both mean "no offset", through has_off = 0 and through adding 0.0."""
+    n, K, fam = c["X"].shape[0], c["K"], c["family"]
+
+    def schedule(it):
+        r = np.random.default_rng(1000 + it)
+        o = r.normal(0, 0.3, n if K == 1 else (K, n))
+        inp = {"lik": c["lik"](r)}
+        if fam == "normal":
+            inp["response"] = c["Y"] - o
+            return inp
+        a, b = (zero_at, none_at) if swap else (none_at, zero_at)
+        inp["offset"] = None if it == a else np.zeros_like(o) if it == b else o
+        return inp
+
+    return schedule
+
+
+def history_sampler(c, backend, in_force):
+    """A FRESH handle of `backend` with the inputs in force (what the setters were last given)."""
+    X, Y = c["X"], c["Y"]
+    st = PyBartSettings.from_data(X, c.get("bart_Y", Y), m=c["m"], num_particles=c["P"], seed=c["seed"], batch=c["batch"],
+                                  family=c["family"], n_outputs=c["K"], response=c["response"], compat=c.get("compat", 0))
+    s = PySampler(st, in_force.get("X", X), in_force.get("response", Y), in_force.get("rules", c["rules"]), c["prior"],
+                  backend=backend)
+    if c.get("setup") is not None:
+        c["setup"](s, in_force)
+    if in_force.get("offset") is not None:
+        s.set_offset(in_force["offset"])
+    if in_force.get("lik") is not None:
+        s.set_likelihood(in_force["lik"])
+    return s
+
+
+def apply_inputs(c, s, inp):
+    if "response" in inp:
+        s.set_response(inp["response"])
+    if "offset" in inp:
+        s.set_offset(inp["offset"])
+    if c.get("apply") is not None:
+        c["apply"](s, inp)
+    if "lik" in inp:
+        s.set_likelihood(inp["lik"])
+
+
+def step_record(c, s, tune):
+    """One astep and everything it gives back, as bytes."""
+    stv, vi = s.step(tune)
+    ta = s.export_trees(0)
+    parts = [ta.tree_id, ta.node_off, ta.var, ta.left, ta.right, ta.count, ta.split.view(np.int64),
+             ta.value.ravel().view(np.int64), ta.slope.ravel().view(np.int64), ta.xbar.view(np.int64), ta.svar]
+    return dict(sum_trees=np.ascontiguousarray(stv).tobytes(), vi=np.asarray(vi, np.int32).tobytes(),
+                trees=b"".join(np.ascontiguousarray(a).tobytes() for a in parts))
+
+
+def end_record(s):
+    from pymc_bart_amd.image import ImageHeader
+
+    stt = s.state()
+    ctr = s.counters.as_dict()
+    ctr.pop("slots")
+    blob = bytearray(s.checkpoint())
+    if s.backend.lib.backend_name == "hip-gfx950":
+        # (`slots` counts launches, idle ones included: it belongs to the handle, not to the chain -- pgbart_image.h)
+        off = ImageHeader.ctr.offset + type(s.counters).slots.offset
+        blob[off: off + 8] = bytes(8)
+    return dict(leaf_sd=np.asarray(stt["leaf_sd"]).tobytes(), iter=stt["iter"], lower=stt["lower"],
+                split_weights=s.split_weights().tobytes(), counters=ctr, image=bytes(blob))
+
+
+def run_schedule(c, schedule, backend, start=0, image=None, in_force=None, cuts=()):
+    """Steps `start` .. steps - 1 of the schedule.  start > 0: on a fresh handle built with `in_force` that loads
+    `image`.  Before every step in `cuts` the image and the inputs in force are kept (the setters of that step have
+    not been called yet)."""
+    in_force = dict(in_force or {})
+    if start == 0:
+        first = schedule(0)
+        s = history_sampler(c, backend, {k: v for k, v in first.items() if k in ("response", "X", "rules")})
+    else:
+        s = history_sampler(c, backend, in_force)
+        s.restore(image)
+    steps, kept = [], {}
+    half = c["steps"] // 2
+    for it in range(start, c["steps"]):
+        if it in cuts:
+            kept[it] = (s.checkpoint(), dict(in_force))
+        inp = schedule(it)
+        apply_inputs(c, s, inp)
+        in_force.update(inp)
+        steps.append(step_record(c, s, it < half))
+    return dict(steps=steps, end=end_record(s), kept=kept, sampler=s)
+
+
+def assert_same_run(a, b, what, first=0, ignore=()):
+    assert len(a["steps"]) == len(b["steps"])
+    for i, (x, y) in enumerate(zip(a["steps"], b["steps"])):
+        for k in x:
+            assert x[k] == y[k], f"{what}: {k} differs at step {first + i}"
+    for k in a["end"]:
+        if k == "image" and a["end"][k] != b["end"][k]:
+            from pymc_bart_amd.image import ChainImage, differing_fields
+
+            ia, ib = ChainImage.parse(a["end"][k]), ChainImage.parse(b["end"][k])
+            if ia.writer != ib.writer:  # two backends: everything but who wrote it and the launch counter
+                bad = [f for f in differing_fields(ia, ib) if f not in ignore]
+                assert bad == [], f"{what}: the end images differ in {bad}"
+                continue
+            raise AssertionError(f"{what}: the end images differ in {differing_fields(ia, ib) or 'bytes outside the chain fields'}")
+        assert a["end"][k] == b["end"][k], f"{what}: {k} differs after the last step"
+
+
+def check_schedule(c, schedule, backend, cuts, reference=None, ignore=()):
+    """The two assertions of the history tests: (1) `backend` equals `reference` (a run of the same schedule on the
+    oracle) on every step's outputs and at the end; (2) at every cut a fresh handle of `backend` -- built with the
+    inputs in force there, then `restore(image)` -- continues identically to the end and ends with the same image.
+    `ignore`: image fields the two backends cannot share (the compiled family is the oracle's callback family: the
+    family code in the settings)."""
+    full = run_schedule(c, schedule, backend, cuts=cuts)
+    assert sorted(full["kept"]) == sorted(cuts)
+    if reference is not None:
+        assert_same_run(full, reference, f"{c['name']}: {backend.lib.backend_name} against the oracle", ignore=ignore)
+    for cut in cuts:
+        image, in_force = full["kept"][cut]
+        tail = run_schedule(c, schedule, backend, start=cut, image=image, in_force=in_force)
+        whole = dict(steps=full["steps"][cut:], end=full["end"])
+        assert_same_run(tail, whole, f"{c['name']}: fresh handle from the image before step {cut}", first=cut)
+    return full
+
+
+def set_data_rc(s, X, rules, prior, ldx=None):
+    """`pgb_set_data` on a live sampler through the ABI: returns (code, message) instead of raising."""
+    lib, mem = s.backend.lib, s.backend.mem
+    X = np.ascontiguousarray(X, np.float64)
+    rules = np.ascontiguousarray(rules, np.int32)
+    prior = np.ascontiguousarray(prior, np.float64)
+    xd = mem.from_host(X)
+    rc = lib.lib.pgb_set_data(s._h, mem.ptr(xd), X.shape[1] if ldx is None else ldx, rules.ctypes.data, prior.ctypes.data)
+    msg = lib.lib.pgb_last_error()
+    if hasattr(mem, "synchronize"):
+        mem.synchronize()
+    del xd
+    s._rules = rules
+    return rc, (msg.decode() if msg and rc != 0 else "")

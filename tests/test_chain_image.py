@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _cases import digest, make_case, run_case
+from _cases import CASES, digest, make_case, run_case
+from _image_edits import EDIT_CASES, image_edits
 from pymc_bart_amd import _abi
 from pymc_bart_amd.image import ChainImage, ImageHeader, differing_fields
 from pymc_bart_amd.sampler import PyBartSettings, PySampler
@@ -141,6 +142,60 @@ def test_damaged_or_foreign_images_are_refused_with_a_message(oracle):
     sa, _ = a.step(False)
     sb, _ = b.step(False)
     assert np.array_equal(sa, sb)
+    for name in EDIT_CASES:  # the same of records that are whole but could not have been written by any backend
+        _edited_images_are_refused(oracle, name)
+
+
+def end_of_run_image(name, oracle, steps=None):
+    c = make_case(name)
+    if steps is not None:
+        c["steps"] = steps
+    return c, run_case(c, oracle, record_every=10 ** 6)["sampler"].checkpoint()
+
+
+def _fresh(c, blob, backend):
+    """A new sampler with the image's own settings (alpha / beta of the case included)."""
+    p = c["X"].shape[1]
+    st = PyBartSettings.from_data(c["X"], c.get("bart_Y", c["Y"]), m=c["m"], num_particles=c["P"], seed=c["seed"],
+                                  batch=c["batch"], alpha=c.get("alpha", 0.95), beta=c.get("beta", 2.0),
+                                  family=c.get("family", "normal"), n_outputs=c.get("K", 1),
+                                  response=c.get("response", "constant"), compat=c.get("compat", 0))
+    assert bytes(st.as_c()) == bytes(ChainImage.parse(blob).header.s)
+    return PySampler(st, c["X"], c["Y"], np.zeros(p, np.int32) if c["rules"] is None else c["rules"],
+                     np.ones(p) if c["prior"] is None else c["prior"], backend=backend)
+
+
+def _edited_images_are_refused(oracle, name):
+    """The table of tests/_image_edits.py on the end-of-run image of one case: every single-field edit a writer never
+    produces is refused by pgb_image_check with its own "checkpoint is inconsistent (...)" text; the sampler that
+    refused them all still loads the good image and continues the chain."""
+    c, blob = end_of_run_image(name, oracle)
+    b = _sampler(c, oracle)
+    edits, skipped = image_edits(blob)
+    assert len(edits) >= 34 and {w for w, _ in skipped} <= {"an orphan row with a label no leaf has",
+                                                           "a node with two parents, another with none"}, skipped
+    if name == "nan_onehot_prior":
+        assert not skipped, skipped  # (this image has orphan rows: every edit of the table applies)
+    for what, bad, text in edits:
+        with pytest.raises(_abi.PGBError, match=r"checkpoint is inconsistent \(.*(" + text + ")"):
+            b.restore(bad)
+            pytest.fail(f"{name}: accepted: {what}")
+    a = _sampler(c, oracle)
+    a.restore(blob)
+    b.restore(blob)
+    for tune in (True, False):
+        sa, va = a.step(tune)
+        sb, vb = b.step(tune)
+        assert np.array_equal(sa, sb) and np.array_equal(va, vb)
+    assert a.checkpoint() == b.checkpoint()
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_no_image_a_writer_produces_is_refused(oracle, name):
+    """The condition on every check of pgb_image_check: the end-of-run image of every parity case loads (NaN rows,
+    empty leaves of the upstream-semantics switches, stumps that won every update, K-vector and linear leaves)."""
+    c, blob = end_of_run_image(name, oracle)
+    _fresh(c, blob, oracle).restore(blob)
 
 
 def test_binding_refuses_a_library_of_another_abi_revision(tmp_path):
@@ -181,3 +236,50 @@ def test_the_forest_of_an_image_predicts_like_the_sampler_it_came_from(oracle):
     ok = ~np.isnan(X).any(axis=1)
     pred = ps.sample_posterior(X[ok], [0])[0, 0]
     np.testing.assert_allclose(pred, img.sum_trees[0][ok], rtol=0, atol=1e-9)
+
+
+FUZZ_IMAGES = [("normal/linear", {"rules": "mixed"}, 11), ("categorical:3/mix", {"rules": "mixed"}, 12),
+               ("poisson_log", {}, 13), ("normal_meanscale:2", {}, 14)]
+
+
+def test_loader_safety_under_the_sanitizers(oracle, tmp_path):
+    """tests/image_fuzz_main.c: the oracle and pgb_image_check compiled with AddressSanitizer and UBSan into a
+    stand-alone program; 2 000 seeded random edits (single bytes, whole fields, truncations) of each of four images
+    go to pgb_checkpoint_load, and whatever is accepted is stepped, exported and saved.  Passes when nothing is
+    reported; the number of accepted edits is printed (most single-bit changes of a number are another valid chain)."""
+    import os
+    import subprocess
+
+    from _cases import make_history_case, moving_inputs, run_schedule
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "image_fuzz"
+    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-std=gnu11",
+                           "-ffp-contract=off", "-DPGB_MAX_PARTICLES=128", "-w", "-I" + os.path.join(root, "include"),
+                           os.path.join(root, "tests", "image_fuzz_main.c"), "-o", str(exe), "-lm"])
+    total = 0
+    for i, (kind, kw, seed) in enumerate(FUZZ_IMAGES):
+        c = make_history_case(kind, n=257, **kw)  # (small: most accepted edits are stepped under the sanitizers)
+        sched = moving_inputs(c)
+        s = run_schedule(c, sched, oracle)["sampler"]
+        off = sched(c["steps"] - 1).get("offset")
+        rules = np.zeros(8 * ((c["X"].shape[1] * 4 + 7) // 8) // 4, np.int32)
+        rules[: c["X"].shape[1]] = c["rules"]
+        st = bytes(s.settings.as_c())
+        case = tmp_path / f"case{i}.bin"
+        case.write_bytes(b"".join([np.int64(len(st)).tobytes(), st, np.ascontiguousarray(c["X"], np.float64).tobytes(),
+                                   np.asarray(s.backend.mem.to_host(s._y), np.float64).tobytes(), rules.tobytes(),
+                                   np.ascontiguousarray(c["prior"], np.float64).tobytes(),
+                                   np.int64(off is not None).tobytes(),
+                                   b"" if off is None else np.ascontiguousarray(off, np.float64).tobytes()]))
+        image = tmp_path / f"image{i}.bin"
+        image.write_bytes(s.checkpoint())
+        r = subprocess.run([str(exe), str(case), str(image), "2000", str(seed)], capture_output=True, text=True,
+                           env={**os.environ, "ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"})
+        print(f"{kind}: {r.stdout.strip()}")
+        assert r.returncode == 0 and r.stderr == "", f"{kind}:\n{r.stdout}\n{r.stderr[-4000:]}"
+        words = r.stdout.split()
+        assert words[0] == "edits" and words[1] == "2000" and words[4] == "failed_after_accept" and words[5] == "0"
+        total += int(words[3])
+    assert 0 < total < 4 * 2000  # some edits are other valid chains, some are refused
+    print(f"accepted edits: {total} of {4 * 2000}")

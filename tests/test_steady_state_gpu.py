@@ -223,3 +223,42 @@ def test_full_size_cfg5_parity_at_steady_state(hip, oracle):
     g, o = _pair(w, hip, oracle, m=100, num_particles=40, batch=(8, 8), family="categorical", n_outputs=4)
     img = _burn_in_then_compare(g, o, 130, [(True, 1), (False, 1)])  # (tune=0 is what bench.py times)
     assert img.header.iter == 1000 and img.node_off[-1] > 3 * 100
+
+
+# ---------------------------------------------------------------- edited images never reach a kernel
+@pytest.mark.parametrize("name", ["ragged_1025", "linear_response", "categorical_k3_mix", "nan_onehot_prior"])
+def test_edited_images_are_refused_before_any_device_access(hip, oracle, name):
+    """The edit table of tests/_image_edits.py.  Every edit goes to the oracle first; only what the oracle refuses is
+    handed to a HIP handle (an edit the oracle accepts fails the test right there, without touching the GPU).  Both
+    loaders call the same pgb_image_check before they touch any state, so the HIP library answers PGB_E_INVALID with
+    the same words and no kernel ever sees the record.  Afterwards the HIP handle loads the good image and continues
+    bit for bit like the handle that wrote it."""
+    from _image_edits import image_edits
+    from pymc_bart_amd import _abi
+    from test_chain_image import _fresh
+
+    c = make_case(name)
+    writer = run_case(c, oracle, record_every=10 ** 6)["sampler"]
+    blob = writer.checkpoint()
+    edits, _ = image_edits(blob)
+    cpu = _fresh(c, blob, oracle)
+    refusals = []
+    for what, bad, text in edits:
+        with pytest.raises(_abi.PGBError, match=r"checkpoint is inconsistent \(") as e:
+            cpu.restore(bad)
+            pytest.fail(f"{name}: the oracle accepted: {what}")
+        refusals.append((what, bad, str(e.value)))
+    g = _fresh(c, blob, hip)
+    assert g.backend.lib.backend_name == "hip-gfx950"
+    if c.get("offset") is not None:
+        g.set_offset(c["offset"])
+    for what, bad, message in refusals:
+        with pytest.raises(_abi.PGBError) as e:
+            g.restore(bad)
+            pytest.fail(f"{name}: the HIP library accepted: {what}")
+        assert str(e.value) == message and "(code -1)" in message, what
+    g.restore(blob)
+    for tune in (True, False, False):
+        _same_step(g, writer, tune)
+    _same_chain_state(g, writer)
+    assert differing_fields(ChainImage.parse(g.checkpoint()), ChainImage.parse(writer.checkpoint())) == []

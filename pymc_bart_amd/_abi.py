@@ -163,6 +163,17 @@ class PointwiseLik(C.Structure):
     ]
 
 
+class PpcLik(C.Structure):
+    """``pgb_ppc_lik`` (include/pgbart_ppc.h)."""
+
+    _fields_ = [
+        ("family", C.c_int32),
+        ("n_params", C.c_int32),
+        ("params_host", C.c_void_p),
+        ("offset_dev", C.c_void_p),
+    ]
+
+
 #: ``pgb_loglik_fn``: int fn(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out)
 LOGLIK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.c_int64, C.POINTER(C.c_double))
@@ -280,6 +291,14 @@ class PGBLibrary:
         f = self.lib.pgb_row_summary
         f.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                       C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def ppc_entry_point(self):
+        """``pgb_ppc_draw`` (include/pgbart_ppc.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_ppc_draw
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(PpcLik), C.c_uint64,
+                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         f.restype = C.c_int
         return f
 

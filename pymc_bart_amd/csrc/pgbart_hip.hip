@@ -51,6 +51,7 @@
 #include "pgbart_psis.h"
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
+#include "pgbart_ppc.h"
 
 #include "pgb_dims.h"
 
@@ -73,3 +74,4 @@
 #include "k_psis.h"
 #include "k_ice.h"
 #include "k_rowsummary.h"
+#include "k_ppc.h"

@@ -20,6 +20,7 @@ MAX_DEPTH = 64
 MAX_PARTICLES = 128  # of the p128 build of the library; the default build takes 64 (PGBLibrary.max_particles)
 MAX_OUTPUTS = 16  # PGB_MAX_OUTPUTS (include/pgbart_spec.h)
 MAX_NODES = 255
+PDP_LDS_MAXB = 256  # PGB_PDP_LDS_MAXB (include/pgbart_pdp.h)
 ABI_VERSION = 6  # PGB_ABI_VERSION of include/pgbart.h this binding was written against
 
 RULE_CONTINUOUS = 0
@@ -283,6 +284,15 @@ class PGBLibrary:
         f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                       C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                       C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def pdp_entry_point(self):
+        """``pgb_predict_pdp`` (include/pgbart_pdp.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_predict_pdp
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                      C.c_void_p]
         f.restype = C.c_int
         return f
 

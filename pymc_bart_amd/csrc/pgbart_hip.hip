@@ -75,3 +75,4 @@
 #include "k_ice.h"
 #include "k_rowsummary.h"
 #include "k_ppc.h"
+#include "k_pdp.h"

@@ -5,8 +5,8 @@ The reference computes these inside its plotting functions (``plot_pdp`` ``utils
 the numbers are not: they are sweeps of posterior predictions -- per covariate ``samples x m x grid``
 tree traversals with every OTHER covariate marginalised out by the trees' own training counts
 (``excluded``) for the PDP, and ``instances x samples x m x n`` traversals for ICE -- i.e. work for
-the ``k_predict`` kernel behind ``PosteriorSampler.sample_posterior`` (the PDP) and for ``k_ice`` behind
-``PosteriorSampler.ice_mean`` (ICE: every curve of a sweep from one fused call).
+the ``k_pdp_walk`` / ``k_pdp_lookup`` kernels behind ``PosteriorSampler.pdp_sweep`` (the PDP) and for ``k_ice`` behind
+``PosteriorSampler.ice_mean`` (ICE) -- every curve of a sweep from one fused call each.
 
 What the functions return is exactly what upstream hands to its axes: per covariate the grid
 ``x`` and the array of predictions; random draws follow the same call pattern (one
@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .utils import _get_posterior_sampler, _resident_rows, _sample_posterior
+from .utils import _get_posterior_sampler, _resident_rows
 
 DEFAULT_QUANTILES = (0.05, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.95)  # upstream's default grid
 
@@ -53,25 +53,40 @@ def _samplers(bart, backend):
     return got if isinstance(bart, list) else got[0]
 
 
-def _summarised(sampler, grid, rng, samples: int, others, spec):
-    """One covariate of :func:`partial_dependence` with ``summary=``: the predictions ``(samples, grid, outputs)`` of
-    the draws ``_sample_posterior`` would pick (the same single ``rng.integers`` call) and their device summary."""
-    from .summary import _Job
+def _summarised(g, grid, cols, picks, spec, keep_pd: bool):
+    """The sweep of one sampler with ``summary=``: ``(pred (n_cols, samples, K, grid) or None, [summary dict per
+    column])``.  Every block of the sweep stays on the device: a column's ``[samples][K * rows]`` part of it is the
+    matrix ``pgb_row_summary`` takes; only with ``keep_pd`` is the block also copied to the host."""
+    from .pdp import _checked, device_blocks
+    from .pointwise import _chains
+    from .summary import _hip, _result, _spec, _summary_block
+    from .trees import pooled_history
 
-    group = sampler if isinstance(sampler, list) else [sampler]
-    picks = rng.integers(0, group[0].n_draws, size=samples)
-    got = [_Job(g, grid, picks, spec[0], spec[1], spec[2], None, others).run(keep_matrix=True) for g in group]
-    pred = got[0][1] if len(got) == 1 else np.concatenate([g[1] for g in got], axis=1)  # (samples, K, grid)
-    res = dict(got[0][0])
-    if len(got) > 1:  # a list of samplers contributes its outputs side by side
-        for key in ("mean", "sd", "var", "quantiles", "hdi"):
-            if res[key] is not None:
-                res[key] = np.concatenate([g[0][key] for g in got], axis=-1)
-    return np.ascontiguousarray(np.moveaxis(pred, 1, 2)), res
+    parts = _chains(g)
+    be = _hip(parts[0]._get_backend())
+    lib, mem = be.lib, be.mem
+    K, m = int(parts[0].n_outputs), int(parts[0].m)
+    cached = getattr(g, "pooled_history", None)
+    pool, table = cached() if cached is not None else pooled_history(parts)
+    D = int(picks.shape[1])
+    q, hdi_k, code = _spec(D, *spec)
+    X, cols, picks = _checked(grid, False, cols, picks, int(np.asarray(table).shape[0]), 0)
+    n = int(X.shape[0])
+    stats = np.empty((cols.size, 2 + q.size + 2, K, n))
+    pred = np.empty((cols.size, D, K, n)) if keep_pd else None
+    for c0, c1, r0, r1, od in device_blocks(be, pool, table, m, K, X, cols, picks):
+        width = K * (r1 - r0)
+        for c in range(c0, c1):
+            md = od[(c - c0) * D * width:(c - c0 + 1) * D * width]  # [D][K][rows of the block]
+            stats[c, :, :, r0:r1] = _summary_block(lib, mem, md, D, width, width, None, code, q, hdi_k).reshape(-1, K, r1 - r0)
+        if keep_pd:
+            pred[c0:c1, :, :, r0:r1] = mem.to_host(od).reshape(c1 - c0, D, K, r1 - r0)
+    return pred, [_result(stats[c], n, K, q, spec[1], hdi_k, D) for c in range(cols.size)]
 
 
 def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs_values=None,
-                       samples: int = 200, func=None, random_seed=None, backend=None, summary=None) -> dict:
+                       samples: int = 200, func=None, random_seed=None, backend=None, summary=None,
+                       keep_pd: bool = True) -> dict:
     """Partial dependence of the BART function on each covariate of ``var_idx``.
 
     For covariate ``j`` the forest is evaluated on the grid with all other covariates excluded:
@@ -80,10 +95,17 @@ def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs
     (samples, grid, outputs)}, "labels": {j: name}, "reference": mean of all partial dependences}``
     (the dashed reference line of the upstream plot).
 
+    The draws of every covariate are chosen first -- one ``rng.integers(0, n_draws, samples)`` per covariate, in
+    covariate order, as one ``_sample_posterior`` call per covariate chose them -- and all of them then come from ONE
+    ``pdp_sweep`` call per sampler (``include/pgbart_pdp.h``: the trees are uploaded once, and a covariate that only
+    ``x <= v`` splits test is evaluated once per interval between its split values, not once per row).
+
     ``summary={"quantiles": ..., "hdi_prob": ..., "transform": ...}`` (every key optional) adds ``out["summary"][j]``:
     the mean, sd, var, quantiles and HDI of ``pd[j]`` over its samples -- arrays ``(grid, outputs)`` -- computed on
-    the device from the same draws by :func:`~pymc_bart_amd.posterior_summary`'s kernel, one predict-plus-summary
-    call per covariate.  ``func`` is a host function and cannot be combined with it: name a ``transform``."""
+    the device from the same draws by :func:`~pymc_bart_amd.posterior_summary`'s kernel, on the sweep where it lies.
+    ``func`` is a host function and cannot be combined with it: name a ``transform``.  ``keep_pd=False`` (with
+    ``summary=`` only) leaves ``pd[j]`` ``None``: nothing of size samples x grid reaches the host -- what makes
+    ``xs_interval="insample"`` usable on large data -- and ``reference`` is the mean of the summaries' means."""
     spec = None
     if summary is not None:
         if func is not None:
@@ -97,29 +119,52 @@ def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs
         spec = (summary.get("quantiles", _summary.DEFAULT_QUANTILES), summary.get("hdi_prob", _summary.DEFAULT_HDI_PROB),
                 summary.get("transform", "identity"))
         _summary._spec(int(samples), *spec)  # (refused before a backend is touched)
+    elif not keep_pd:
+        raise ValueError("keep_pd=False leaves nothing to return without summary=: name the summaries to keep")
     Xm, names = _as_matrix(X)
     p = Xm.shape[1]
     cols = list(range(p)) if var_idx is None else [int(v) for v in var_idx]
     sampler = _samplers(bart, backend)
+    group = sampler if isinstance(sampler, list) else [sampler]
     rng = np.random.default_rng(random_seed)
     grid = pdp_grid(Xm, xs_interval, xs_values)
-    rows = _resident_rows(sampler, grid) if spec is None else None  # one upload for the sweep over the covariates
     out = {"x": {}, "pd": {}, "labels": {}, "reference": None}
     if spec is not None:
         out["summary"] = {}
+    if not cols:
+        return out
+    picks = np.stack([rng.integers(0, group[0].n_draws, size=int(samples)) for _ in cols])
+    if spec is None:
+        rows = _resident_rows(sampler, grid) if len(group) > 1 else grid  # (several samplers: one upload for all)
+        preds = [g.pdp_sweep(rows, cols, picks) for g in group]  # (n_cols, samples, K_g, grid)
+        summaries = None
+    else:
+        got = [_summarised(g, grid, cols, picks, spec, keep_pd) for g in group]
+        preds = [pr for pr, _ in got] if keep_pd else None
+        summaries = got[0][1]
+        for c in range(len(cols) if len(got) > 1 else 0):  # a list of samplers contributes its outputs side by side
+            for key in ("mean", "sd", "var", "quantiles", "hdi"):
+                if summaries[c][key] is not None:
+                    summaries[c][key] = np.concatenate([sm[c][key] for _, sm in got], axis=-1)
+    stacked = None
+    if preds is not None:
+        stacked = preds[0] if len(preds) == 1 else np.concatenate(preds, axis=2)
     means = []
-    for j in cols:
-        others = [v for v in range(p) if v != j]
-        if spec is not None:
-            pd_j, out["summary"][j] = _summarised(sampler, grid, rng, int(samples), others, spec)
+    for c, j in enumerate(cols):
+        pd_j = None
+        if stacked is not None:
+            pd_j = np.ascontiguousarray(np.moveaxis(stacked[c], 1, 2))  # (samples, grid, K)
+            if func is not None:
+                pd_j = func(pd_j)
+            means += [float(pd_j[:, :, k].mean()) for k in range(pd_j.shape[2])]
         else:
-            pd_j = _sample_posterior(sampler, X=rows, rng=rng, size=samples, excluded=others)
-        if func is not None:
-            pd_j = func(pd_j)
+            mean_j = summaries[c]["mean"]
+            means += [float(mean_j[:, k].mean()) for k in range(mean_j.shape[1])]
+        if summaries is not None:
+            out["summary"][j] = summaries[c]
         out["x"][j] = grid[:, j]
         out["pd"][j] = pd_j
         out["labels"][j] = names[j]
-        means += [float(pd_j[:, :, k].mean()) for k in range(pd_j.shape[2])]
     out["reference"] = float(np.mean(means)) if means else None
     return out
 

@@ -416,3 +416,15 @@ class PosteriorSampler:
 
         return ice_mean(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, self.sample_posterior,
                         X, instances, cols, picks)
+
+    def pdp_sweep(self, X, cols, picks, route: int = 0, taken=None) -> np.ndarray:
+        """Partial dependence sweeps, ``(n_cols, n_picks, n_outputs, n_rows)``: entry ``[c, s, k, i]`` is output ``k``
+        of the draw ``picks[c, s]`` predicted at ``X[i, cols[c]]`` with every other column excluded -- the bits of
+        ``sample_posterior(X, picks[c], all but cols[c])``.  ``X`` may be a handle from :meth:`resident_rows`; picks
+        may repeat.  On the HIP backend this is one fused ``pgb_predict_pdp`` call per block (the device output stays
+        under ``PGB_PDP_BLOCK_BYTES``, default 1 GiB: whole columns first, rows of one column when it does not fit;
+        results depend neither on the blocking nor on ``route``, see ``pdp.pdp_sweep``)."""
+        from .pdp import pdp_sweep
+
+        return pdp_sweep(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, self.sample_posterior,
+                         X, cols, picks, route, taken)

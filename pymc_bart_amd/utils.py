@@ -128,6 +128,15 @@ class _MultiChainSampler:
         return ice_mean(first._get_backend(), pool, table, first.m, first.n_outputs, self.sample_posterior,
                         X, instances, cols, picks)
 
+    def pdp_sweep(self, X, cols, picks, route: int = 0, taken=None) -> np.ndarray:
+        """``PosteriorSampler.pdp_sweep`` over the concatenated history: ``picks`` index the draws of all chains."""
+        from .pdp import pdp_sweep
+
+        first = self._parts[0]
+        pool, table = self.pooled_history()
+        return pdp_sweep(first._get_backend(), pool, table, first.m, first.n_outputs, self.sample_posterior,
+                         X, cols, picks, route, taken)
+
     def sample_posterior(self, X, draw_indices, excluded):
         want = np.asarray(draw_indices, dtype=np.int64).ravel()
         owner = np.digitize(want, self._starts[1:])  # chain of every requested draw

@@ -147,6 +147,27 @@ __global__ __launch_bounds__(256) void k_probe(ProbeArgs A) {
   }
 }
 
+// The split-variable draw of k_ctrl on weights the caller supplies, one wave per threshold (four to a workgroup,
+// as the control kernel's waves are): mode 0 sample_var_prefix on stored prefix sums -- the loop up to 64 columns,
+// the four blocks requested together up to 256, the loop again beyond --, mode 1 sample_var_weights on the weights
+// themselves (the 64-wide scan with its carry, as while the sampler is rebuilt).  The draw is wave-uniform: lane 0
+// writes it, and whether any lane holds another value.
+__global__ __launch_bounds__(256) void k_probe_sample_var(const long long* __restrict__ A, const long long* __restrict__ S,
+                                                          int p, const double* __restrict__ u, long long n, int mode,
+                                                          int* __restrict__ out, int* __restrict__ differ) {
+  const int wave = threadIdx.x >> 6;
+  for (long long i = (long long)blockIdx.x * 4 + wave; i < n; i += (long long)gridDim.x * 4) {  // (wave-uniform)
+    const double ui = u[i];
+    const int j = mode ? sample_var_weights(A, p, ui) : sample_var_prefix(S, p, ui);
+    const int j0 = __builtin_amdgcn_readfirstlane(j);
+    const unsigned long long other = __ballot(j != j0);
+    if ((threadIdx.x & 63) == 0) {
+      out[i] = j0;
+      differ[i] = other != 0ull;
+    }
+  }
+}
+
 namespace probe {
 struct Stage {  // device copies of the caller's host arrays, freed on scope exit
   std::vector<void*> bufs;
@@ -344,5 +365,32 @@ int pgbh_go_left(int rule, const double* x, const double* v, int64_t n, int64_t*
   int rc = probe::run(A, st);
   if (rc == PGB_OK) st.back((long long*)out, A.oi, n);
   return st.ok ? rc : fail(PGB_E_DEVICE, "probe: copy failed");
+}
+/* the split-variable draw on integer split weights (tests/test_spec_device_gpu.py): mode 0 from their prefix sums,
+ * mode 1 from the weights themselves; out[i] = the column drawn by threshold u[i] */
+int pgbh_sample_var(const int64_t* weights, int p, const double* u, int64_t n, int mode, int32_t* out) {
+  if (!weights || !u || !out || p < 1 || n < 0 || (mode != 0 && mode != 1)) return fail(PGB_E_INVALID, "probe: sample_var arguments");
+  if (n == 0) return PGB_OK;
+  std::vector<long long> cdf((size_t)p);
+  long long run = 0;
+  for (int j = 0; j < p; ++j) cdf[(size_t)j] = run += (long long)weights[j];
+  probe::Stage st;
+  const long long* dA = st.in((const long long*)weights, p);
+  const long long* dS = st.in(cdf.data(), p);
+  const double* du = st.in(u, n);
+  int* dout = st.out<int>(n);
+  int* ddiff = st.out<int>(n);
+  if (!st.ok) return fail(PGB_E_DEVICE, "probe: staging failed");
+  long long g = (n + 3) / 4;
+  if (g > 4096) g = 4096;
+  hipLaunchKernelGGL(k_probe_sample_var, dim3((unsigned)g), dim3(256), 0, 0, dA, dS, p, du, (long long)n, mode, dout, ddiff);
+  if (hipDeviceSynchronize() != hipSuccess) return fail(PGB_E_DEVICE, "probe: kernel failed");
+  std::vector<int> diff((size_t)n);
+  st.back((int*)out, dout, n);
+  st.back(diff.data(), ddiff, n);
+  if (!st.ok) return fail(PGB_E_DEVICE, "probe: copy failed");
+  for (int64_t i = 0; i < n; ++i)
+    if (diff[(size_t)i]) return fail(PGB_E_DEVICE, "probe: the lanes of a wave disagree on the split variable");
+  return PGB_OK;
 }
 }  // extern "C"

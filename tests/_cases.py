@@ -307,8 +307,10 @@ CASES = ["cfg1_friedman", "nan_onehot_prior", "ragged_1025", "tiny_n3", "one_tre
          "upstream/categorical_k3_linear_mixed_rules", "upstream/particles_128", "upstream/logit_nan_onehot"]
 
 
-def run_case(c, backend, record_every: int = 1, checkpoint_at=()):
+def run_case(c, backend, record_every: int = 1, checkpoint_at=(), setup=None):
     """Run the case on a backend; returns everything the two backends must agree on.
+    ``setup``: called with every freshly built sampler before anything else is done with it (e.g. to hand the
+    data over again in another layout).
     ``checkpoint_at``: step indices before which the chain is checkpointed, its sampler destroyed
     and a freshly built sampler restored from the image (must not change anything); a dict
     ``{step: backend}`` moves the chain to ANOTHER backend there (the image belongs to none:
@@ -323,10 +325,13 @@ def run_case(c, backend, record_every: int = 1, checkpoint_at=()):
     rules = np.zeros(p, np.int32) if c["rules"] is None else c["rules"]
     prior = np.ones(p) if c["prior"] is None else c["prior"]
     s = PySampler(st, X, Y, rules, prior, backend=backend)
+    if setup is not None:
+        setup(s)
     if c.get("offset") is not None:
         s.set_offset(c["offset"])
+    weights0 = s.split_weights()
     sig_rng = np.random.default_rng(99)
-    sums, vis, trees = [], [], []
+    sums, vis, trees, split_vars = [], [], [], []
     half = c["steps"] // 2
     for it in range(c["steps"]):
         if it in checkpoint_at:
@@ -335,6 +340,8 @@ def run_case(c, backend, record_every: int = 1, checkpoint_at=()):
             if isinstance(checkpoint_at, dict):
                 backend = checkpoint_at[it]
             s = PySampler(st, X, Y, rules, prior, backend=backend)
+            if setup is not None:
+                setup(s)
             if c.get("offset") is not None:
                 s.set_offset(c["offset"])
             s.restore(blob)
@@ -350,11 +357,13 @@ def run_case(c, backend, record_every: int = 1, checkpoint_at=()):
             if c.get("response", "constant") != "constant":  # linear leaves are part of the fingerprint
                 parts += [ta.slope.ravel().view(np.int64), ta.xbar.view(np.int64), ta.svar]
             trees.append(np.concatenate(parts))
+            split_vars.append(np.asarray(ta.var)[np.asarray(ta.var) >= 0].astype(np.int64))
     forest = s.export_trees(1)
     ctr = s.counters.as_dict()
     ctr.pop("slots")
     return dict(sum_trees=np.array(sums), vi=np.array(vis), trees=trees, forest=forest, counters=ctr,
-                state=s.state(), split_weights=s.split_weights(), sampler=s)
+                state=s.state(), split_weights=s.split_weights(), sampler=s, split_vars=split_vars,
+                split_weights_init=weights0)
 
 
 def digest(res) -> dict:
@@ -658,3 +667,111 @@ def set_data_rc(s, X, rules, prior, ldx=None):
     del xd
     s._rules = rules
     return rc, (msg.decode() if msg and rc != 0 else "")
+
+
+# ------------------------------------------------------------------ wide design matrices (tests/test_wide*.py)
+# The sampler's device code branches on the column count p: the split-variable draw in blocks of 64 lanes (one loop
+# up to 64, four blocks requested together up to 256, the loop again beyond), the 64-bit carry between the blocks
+# while the prefix sums are rebuilt in tuning, the 32 x 32 tiles of the transpose, one workgroup per column in the
+# checks, `vi` copied in trips of 256 and laid out in 64-byte lines, the split prior staged in a row buffer when
+# p < n_pad and in an allocation of its own when p >= n_pad.  Every p below sits on one of those edges.
+WIDE_P = [31, 32, 33, 63, 64, 65, 255, 256, 257, 300, 1023, 1024, 1025, 1500]
+WIDE_VARIANTS = ["normal", "linear", "probit_mix", "categorical_k3", "normal_p100"]
+WIDE_HOT = (0, 31, 32, 63, 64, 65, 255, 256, 257)   # ... and p - 1
+WIDE_ROWS = {257: 1025, 1025: 1025}                # two chunks (n_pad = 2048: p = 1025 < n_pad); every other p: 130 rows
+# (p, variant) -> the first seed whose oracle run meets check_wide_reach, where seed 0 does not
+WIDE_SEEDS = {(63, "categorical_k3"): 1, (64, "linear"): 1, (255, "normal"): 1, (256, "normal"): 1, (257, "categorical_k3"): 3,
+              (1023, "linear"): 2, (1024, "normal"): 3, (1024, "linear"): 1, (1025, "normal"): 1, (1025, "linear"): 2,
+              (1025, "probit_mix"): 13, (1025, "categorical_k3"): 9, (1500, "normal"): 2, (1500, "linear"): 5,
+              (1500, "probit_mix"): 7, (1500, "categorical_k3"): 1, (1500, "normal_p100"): 1}
+
+
+def wide_layout(p):
+    """(hot columns, one-hot column or None, subset column or None, NaN column) of the p-column wide case."""
+    hot = sorted({h for h in WIDE_HOT + (p - 1,) if 0 <= h < p})
+    late = [h for h in hot if h > 256]
+    if len(late) < 2:
+        late = [h for h in hot if h > 64]
+    onehot, subset = (late[0], late[-1]) if len(late) >= 2 else (None, None)
+    return hot, onehot, subset, p - 1   # (p - 1 is hot, and the last column of the last transpose tile)
+
+
+def wide_case(p, variant, seed):
+    """n = 130 rows (1025 for two widths), m = 3 trees all re-sampled at every step, 12 steps of which 6 tune:
+    iter > m is reached while tuning, so the split-variable draw runs on the weights being rebuilt.  Column j is
+    scaled by 10^(j % 7 - 3); the hot columns carry the signal and a large split prior."""
+    rng = np.random.default_rng([int(p), WIDE_VARIANTS.index(variant), int(seed)])
+    n = WIDE_ROWS.get(p, 130)
+    hot, onehot, subset, nancol = wide_layout(p)
+    scale = 10.0 ** (np.arange(p) % 7 - 3)
+    Z = rng.normal(size=(n, p))
+    rules = np.zeros(p, np.int32)
+    if onehot is not None:
+        Z[:, onehot] = rng.integers(0, 3, n)
+        Z[:, subset] = rng.integers(0, 7, n)
+        rules[onehot], rules[subset] = 1, 2
+    X = Z * scale
+    if onehot is not None:
+        X[:, onehot], X[:, subset] = Z[:, onehot], Z[:, subset]   # category codes are not scaled
+    X[rng.random(n) < 0.15, nancol] = np.nan
+    prior = np.ones(p)
+    prior[hot] = max(4.0, 0.25 * (p - len(hot)) / len(hot))       # the hot columns: a fifth of the prior mass or more
+    f = np.zeros(n)
+    for k, h in enumerate(hot):
+        z = np.nan_to_num(Z[:, h])
+        sgn = 1.0 if k % 2 == 0 else -1.0
+        if h == onehot:
+            f += 1.5 * sgn * (z == 1)
+        elif h == subset:
+            f += 1.5 * sgn * np.isin(z, [1, 4])
+        elif variant == "linear" and h >= 32:
+            f += 0.8 * sgn * np.where(z < 0, z, -0.5 * z)
+        else:
+            f += 1.5 * sgn * (z > 0)
+    c = dict(name=f"wide/p{p}/{variant}", m=3, P=10, steps=12, batch=(1.0, 1.0), rules=rules, prior=prior,
+             seed=1000 + int(seed), beta=0.7, X=X)
+    if variant in ("normal", "linear", "normal_p100"):
+        c.update(Y=f + rng.normal(0, 0.3, n))
+        if variant == "linear":
+            c.update(response="linear")
+        elif variant == "normal_p100":
+            c.update(P=100)
+    elif variant == "probit_mix":
+        from scipy.special import ndtr
+        c.update(Y=(rng.random(n) < ndtr(f)).astype(float), family="bernoulli_probit", response="mix")
+    elif variant == "categorical_k3":
+        logits = np.stack([f, -f, np.zeros(n)]) + rng.gumbel(size=(3, n))
+        c.update(Y=np.argmax(logits, axis=0).astype(float), family="categorical", K=3)
+    else:
+        raise KeyError(variant)
+    return c
+
+
+def make_wide(p, variant):
+    return wide_case(p, variant, WIDE_SEEDS.get((p, variant), 0))
+
+
+def wide_reach(c, res):
+    """What a run of a wide case reached, from its result alone: the 64-blocks of columns its exported trees split
+    on, whether tuning changed a split weight of the last block, `vi` beyond column 255, splits on the NaN column."""
+    p = c["X"].shape[1]
+    sv = np.concatenate(res["split_vars"]) if len(res["split_vars"]) else np.zeros(0, np.int64)
+    last = 64 * ((p - 1) // 64)
+    changed = np.flatnonzero(res["split_weights"] != res["split_weights_init"])
+    return dict(p=p, n_blocks=(p + 63) // 64, blocks=sorted({int(v) // 64 for v in sv}), n_splits=int(sv.size),
+                beyond_31=int((sv >= 32).sum()), last_column=int((sv == p - 1).sum()),
+                nan_column=int((sv == wide_layout(p)[3]).sum()),
+                tuned_in_last_block=int((changed >= last).sum()),
+                vi_beyond_255=int(np.asarray(res["vi"])[:, 256:].sum()))
+
+
+def check_wide_reach(c, res):
+    """The conditions a wide case exists for (no pytest here: the golden generator calls it too)."""
+    r = wide_reach(c, res)
+    assert r["blocks"] == list(range(r["n_blocks"])), f"{c['name']}: no split in some 64-block of the columns: {r}"
+    assert r["beyond_31"] > 0 or r["p"] <= 32, f"{c['name']}: no split beyond the first transpose tile: {r}"
+    assert r["last_column"] > 0 and r["nan_column"] > 0, f"{c['name']}: no split on the last (NaN) column: {r}"
+    assert r["tuned_in_last_block"] > 0, f"{c['name']}: tuning did not reach the last 64-block: {r}"
+    assert r["vi_beyond_255"] > 0 or r["p"] <= 256, f"{c['name']}: vi is zero beyond column 255: {r}"
+    return r
+

@@ -2,7 +2,9 @@
 """Generate tests/golden/oracle_runs.json: exact fingerprints of the CPU oracle on the seeded
 parity cases of tests/_cases.py.  The HIP backend must reproduce them bit for bit
 (tests/test_parity_gpu.py), and the oracle itself is regression-pinned against them on CPU
-(tests/test_oracle_golden.py)."""
+(tests/test_oracle_golden.py).  Likewise tests/golden/wide_runs.json for the wide design matrices
+(tests/test_wide.py, tests/test_wide_gpu.py): a case is written only if its run reaches the column
+edges it exists for (check_wide_reach)."""
 import json
 import os
 import sys
@@ -11,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
-from _cases import CASES, digest, make_case, run_case  # noqa: E402
+from _cases import (CASES, WIDE_P, WIDE_VARIANTS, check_wide_reach, digest, make_case, make_wide,  # noqa: E402
+                    run_case)
 from _oracle import oracle_backend  # noqa: E402
 
 out = {}
@@ -20,3 +23,14 @@ for name in CASES:
     out[name] = digest(res)
     print(name, out[name]["sha256"][:16], out[name]["counters"])
 json.dump(out, open(os.path.join(HERE, "oracle_runs.json"), "w"), indent=1)
+
+wide = {}
+for p in WIDE_P:
+    for variant in WIDE_VARIANTS:
+        c = make_wide(p, variant)
+        res = run_case(c, oracle_backend())
+        r = check_wide_reach(c, res)
+        wide[c["name"]] = digest(res)
+        print(c["name"], wide[c["name"]]["sha256"][:16], f"splits in blocks {r['blocks'][0]}..{r['blocks'][-1]} of {r['n_blocks']},",
+              f"{r['last_column']} on column p - 1, {r['tuned_in_last_block']} weights of the last block tuned")
+json.dump(wide, open(os.path.join(HERE, "wide_runs.json"), "w"), indent=1)

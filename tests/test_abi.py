@@ -86,3 +86,18 @@ def test_both_builds_of_the_hip_library_export_the_abi_and_state_their_particle_
         assert lib.backend_name == "hip-gfx950" and lib.max_particles == want
         for sym in _abi.SYMBOLS:
             assert hasattr(lib.lib, sym), (want, sym)
+
+
+# the device probes of tests/test_spec_device_gpu.py: test hooks of the HIP library, not part of the sampler ABI
+PROBE_HOOKS = ["pgbh_loglikq", "pgbh_loglik_bern_lds", "pgbh_loglik_multi", "pgbh_loglik_multi_lds", "pgbh_loglik_cat_f",
+               "pgbh_order_keys", "pgbh_math_t", "pgbh_log_ndtr", "pgbh_math", "pgbh_normal2", "pgbh_draw2", "pgbh_quant",
+               "pgbh_leaf", "pgbh_lin", "pgbh_go_left", "pgbh_sample_var"]
+
+
+def test_both_builds_of_the_hip_library_export_the_probe_hooks():
+    src = open(os.path.join(ROOT, "pymc_bart_amd", "csrc", "pgb_probe.h")).read()
+    assert sorted(set(re.findall(r"^int (pgbh_[a-z_0-9]+)\(", src, flags=re.M))) == sorted(PROBE_HOOKS)
+    for want in (64, 128):
+        lib = _abi.load_hip_library(want)
+        for sym in PROBE_HOOKS:
+            assert hasattr(lib.lib, sym), (want, sym)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import test_spec_independent as T
+import test_wide as W
 from pymc_bart_amd import _abi
 
 pytestmark = pytest.mark.gpu
@@ -358,3 +359,22 @@ def test_order_keys_decide_like_the_values_or_abstain(hip, kind):
     if kind == "normal":
         share = np.bincount(ks).max() / xs.size
         assert share < 20 / 65535                               # equi-depth: ~3 rows per key here, never dozens
+
+
+@pytest.mark.parametrize("p", [1] + W.WIDE_P)
+def test_split_variable_draw_device_equals_numpy_and_host(hip, oracle, p):
+    """`sample_var_prefix` (stored prefix sums: the loop up to 64 columns, four blocks requested together up to 256,
+    the loop again beyond) and `sample_var_weights` (the weights themselves, a 64-wide scan with a 64-bit carry between
+    the blocks: the draw while the sampler is rebuilt) of k_ctrl.h, one wave per threshold, on the vectors of
+    tests/test_wide.py: thresholds exactly on, just below and just above every prefix sum.  Every lane of the wave
+    must hold the same column (the hook fails otherwise)."""
+    A, u = W.split_draw_vectors(p)
+    want = W.numpy_sample_var(A, u)
+    assert np.array_equal(W.oracle_sample_var(oracle, A, u), want)
+    f = _fn(hip.lib.lib, "pgbh_sample_var", C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
+    for mode, what in ((0, "sample_var_prefix"), (1, "sample_var_weights")):
+        got = np.full(u.size, -1, np.int32)
+        assert f(A.ctypes.data, p, u.ctypes.data, u.size, mode, got.ctypes.data) == 0, hip.lib.lib.pgb_last_error()
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, f"{what}, p = {p}: {bad.size} of {u.size} draws differ, first u = {u[bad[0]]!r}: " \
+                              f"device {got[bad[0]]}, NumPy {want[bad[0]]}"

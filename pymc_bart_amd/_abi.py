@@ -21,6 +21,7 @@ MAX_PARTICLES = 128  # of the p128 build of the library; the default build takes
 MAX_OUTPUTS = 16  # PGB_MAX_OUTPUTS (include/pgbart_spec.h)
 MAX_NODES = 255
 PDP_LDS_MAXB = 256  # PGB_PDP_LDS_MAXB (include/pgbart_pdp.h)
+SHAP_FAST_U = 8  # PGB_SHAP_FAST_U (include/pgbart_shap.h)
 ABI_VERSION = 6  # PGB_ABI_VERSION of include/pgbart.h this binding was written against
 
 RULE_CONTINUOUS = 0
@@ -293,6 +294,18 @@ class PGBLibrary:
         f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                       C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                       C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def shap_entry_point(self):
+        """``pgb_predict_shap`` (include/pgbart_shap.h): HIP library only, hence not in SYMBOLS.  A library without
+        the symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_predict_shap
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_predict_shap (HIP library only)") from None
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         f.restype = C.c_int
         return f
 

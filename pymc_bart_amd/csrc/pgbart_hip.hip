@@ -52,6 +52,7 @@
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
 #include "pgbart_ppc.h"
+#include "pgbart_shap.h"
 
 #include "pgb_dims.h"
 
@@ -76,3 +77,4 @@
 #include "k_rowsummary.h"
 #include "k_ppc.h"
 #include "k_pdp.h"
+#include "k_shap.h"

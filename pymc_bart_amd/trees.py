@@ -428,3 +428,15 @@ class PosteriorSampler:
 
         return pdp_sweep(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, self.sample_posterior,
                          X, cols, picks, route, taken)
+
+    def shap(self, X, picks):
+        """Exact Shapley attributions, ``(values (n_picks, n_outputs, n_rows, p), base (n_picks, n_outputs))``: entry
+        ``[s, k, i, j]`` is the share of column ``j`` in output ``k`` of the draw ``picks[s]`` at row ``i``, the value of
+        a coalition being ``sample_posterior`` with every column outside it excluded; ``base`` is the prediction with
+        every column excluded, and ``base + values.sum(-1)`` the plain prediction (``include/pgbart_shap.h``).  ``X`` may
+        be a handle from :meth:`resident_rows`; picks may repeat.  One ``pgb_predict_shap`` call per block of rows (the
+        device output stays under ``PGB_SHAP_BLOCK_BYTES``, default 1 GiB; results do not depend on the blocking).  HIP
+        backend only."""
+        from .shap import shap_sweep
+
+        return shap_sweep(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, X, picks)

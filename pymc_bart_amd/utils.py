@@ -137,6 +137,14 @@ class _MultiChainSampler:
         return pdp_sweep(first._get_backend(), pool, table, first.m, first.n_outputs, self.sample_posterior,
                          X, cols, picks, route, taken)
 
+    def shap(self, X, picks):
+        """``PosteriorSampler.shap`` over the concatenated history: ``picks`` index the draws of all chains."""
+        from .shap import shap_sweep
+
+        first = self._parts[0]
+        pool, table = self.pooled_history()
+        return shap_sweep(first._get_backend(), pool, table, first.m, first.n_outputs, X, picks)
+
     def sample_posterior(self, X, draw_indices, excluded):
         want = np.asarray(draw_indices, dtype=np.int64).ravel()
         owner = np.digitize(want, self._starts[1:])  # chain of every requested draw

@@ -30,10 +30,16 @@
  *                                   on either build.  The Python binding picks the build by num_particles.
  *   n_outputs (K)        1 .. 16   (PGB_MAX_OUTPUTS; K = 2, 3, 4 have unrolled kernel instances, any other K runs in
  *                                  tiles of four outputs: no K-sized array in registers, no scratch)
- *   nodes per tree       <= 255    (leaf labels are bytes; label 255 = dropped row); a tree that
- *                                   would grow past it stops splitting (P ~ 0 under the prior)
+ *   nodes per tree       <= 255    (PGB_MAX_NODES: node tables of 255 entries.  A row's label is a byte: the ordinal of
+ *                                   its leaf, the left child keeping its parent's -- 0 .. 127 in a full tree -- or 255
+ *                                   for a dropped row); a tree that would grow past it stops splitting (P ~ 0 under
+ *                                   the prior).  Held by tests/test_caps.py and tests/test_caps_gpu.py: chains whose
+ *                                   accepted trees stop at 255 nodes with leaves that would still split
  *   tree depth           <= 64     (prior_leaf[64]; upstream cuts its table where P(leaf) >= 0.9999,
- *                                   depth ~ 97 at alpha = 0.95, beta = 2: entries beyond 64 are 1)
+ *                                   depth ~ 97 at alpha = 0.95, beta = 2: entries beyond 64 are 1).  Held by the same
+ *                                   two files: chains that keep rows in leaves at depth 64, and the oracle run under
+ *                                   sanitizers with strict bounds on the table; the prediction walk's side of both
+ *                                   limits by tests/test_predict_edges_gpu.py
  *   SubsetSplit columns  integer category codes 0 .. 51 or NaN (the split value is a 52-bit mask in a double);
  *                        pgb_set_data checks every value and returns PGB_E_INVALID naming the column
  *   response linear/mix  any split rule (a leaf regresses on the column its parent split on, upstream's

@@ -332,7 +332,7 @@ def run_case(c, backend, record_every: int = 1, checkpoint_at=(), setup=None):
     weights0 = s.split_weights()
     sig_rng = np.random.default_rng(99)
     sums, vis, trees, split_vars = [], [], [], []
-    half = c["steps"] // 2
+    half = c.get("tune_steps", c["steps"] // 2)   # ("tune_steps": the schedule of a longer run, cut short)
     for it in range(c["steps"]):
         if it in checkpoint_at:
             blob = s.checkpoint()
@@ -460,6 +460,55 @@ def random_case(seed, large=False, compat=0):
     return dict(**extra, name=f"fuzz{seed}", compat=int(compat), response=response, X=X, Y=Y, m=m, P=P, steps=int(rng.integers(2, 5) if large else rng.integers(4, 14)), batch=batch, rules=rules,
                 prior=rng.uniform(0.5, 3.0, p), seed=int(rng.integers(0, 2**31)), family=fam, K=K,
                 alpha=float(rng.choice([0.95, 0.5, 0.999])), beta=float(rng.choice([2.0, 0.5, 1.0])))
+
+
+def random_cap_case(seed):
+    """A random configuration at the tree-size limits for the fuzz parity test (tests/test_caps_gpu.py): the data of
+    cap_case at row counts around the chunk / wave boundaries, 2 .. 128 particles, missing values, the upstream
+    switches, alpha = 0.9999 with beta = 0 or 0.05 (P(split) >= 0.81 down to depth 64).  Every tree is re-sampled at
+    every step, so cap_reach reads the run."""
+    rng = np.random.default_rng([77, int(seed)])
+    n = int(rng.choice([128, 129, 255, 257, 1025, 2049]))
+    # the one-hot column needs rows in 65 codes and more: the small row counts mostly take the continuous columns
+    kind = str(rng.choice(["bushy", "chain", "both"], p=[0.8, 0.1, 0.1] if n < 1025 else [0.3, 0.3, 0.4]))
+    fam = str(rng.choice(["normal", "normal", "bernoulli_probit", "categorical", "poisson_log"]))
+    if kind == "chain" and fam == "bernoulli_probit":   # (leaves only the stump on the pure one-hot column)
+        fam = "normal"
+    response = str(rng.choice(["constant", "constant", "linear", "mix"]))
+    P = int(rng.choice([2, 10, 64, 65, 128], p=[0.1, 0.3, 0.2, 0.2, 0.2]))   # (two particles mostly keep the stump)
+    nan_frac = float(rng.choice([0.0, 0.0, 0.05, 0.3]))
+    compat = int(rng.choice([0, 0, 1, 2, 3]))
+    beta = float(rng.choice([0.0, 0.05], p=[0.75, 0.25]))
+    if kind != "bushy" or n < 255:   # P(split) = 0.81 at depth 64 under beta = 0.05: no chain of 64, no 255 nodes from 129 rows
+        beta = 0.0
+    code = rng.integers(0, 100, n).astype(float)
+    z = rng.normal(size=(n, 2))
+    fc = np.sin(0.7 * code) + 0.02 * code
+    fz = np.sin(3 * z[:, 0]) + np.where(z[:, 1] < 0, z[:, 1], -0.5 * z[:, 1])
+    if kind == "chain":
+        X, rules, prior, f = code[:, None].copy(), np.array([1], np.int32), np.ones(1), fc
+    elif kind == "bushy":
+        X, rules, prior, f = z.copy(), np.zeros(2, np.int32), np.ones(2), fz
+    else:
+        X, rules, prior, f = np.stack([code, z[:, 1]], axis=1), np.array([1, 0], np.int32), np.array([20.0, 1.0]), fc + fz
+    if nan_frac > 0:
+        X[rng.random(n) < nan_frac, 0] = np.nan
+    K, extra = 1, {}
+    if fam == "normal":
+        Y = f + rng.normal(0, 0.3, n)
+    elif fam == "bernoulli_probit":
+        from scipy.special import ndtr
+        Y = (rng.random(n) < ndtr(2.0 * f)).astype(float)
+    elif fam == "poisson_log":
+        Y = rng.poisson(np.exp(np.clip(f, -3, 3))).astype(float)
+        extra["bart_Y"] = np.log(Y + 0.5)
+    else:
+        K = int(rng.integers(2, 6))
+        logits = np.stack([2.0 * f * (k - 0.5 * (K - 1)) for k in range(K)]) + rng.gumbel(size=(K, n))
+        Y = np.argmax(logits, axis=0).astype(float)
+    return dict(**extra, name=f"capfuzz{seed}", kind=kind, variant=fam, X=X, Y=Y, m=int(rng.integers(1, 4 if P < 64 else 3)), P=P,
+                steps=int(rng.integers(6, 13 if P < 64 else 9)), batch=(1.0, 1.0), rules=rules, prior=prior, seed=int(rng.integers(0, 2 ** 31)),
+                family=fam, K=K, response=response, compat=compat, alpha=0.9999, beta=beta)
 
 
 # ------------------------------------------------------------------ handle history (tests/test_handle_history*.py)
@@ -775,3 +824,187 @@ def check_wide_reach(c, res):
     assert r["vi_beyond_255"] > 0 or r["p"] <= 256, f"{c['name']}: vi is zero beyond column 255: {r}"
     return r
 
+
+
+# ------------------------------------------------------------------ tree-size limits (tests/test_caps*.py)
+# The sampler stops a tree at PGB_MAX_NODES = 255 nodes (node tables of 255 entries, the last index 254; a row's
+# label is a byte, the ordinal of its leaf -- 0 .. 127 in a full tree -- or 255 for a dropped row) and at
+# PGB_MAX_DEPTH = 64 (prior_leaf[64]; a node at depth 64 is a leaf with probability 1).  With alpha = 0.9999, beta = 0
+# a node splits whenever it can, so a few steps of a tiny forest drive the accepted trees into both limits: the
+# guards of the control kernel, label tables filled for 128 leaves next to label 255, the full particle tables, the
+# export and the chain image.
+CAP_MAX_NODES, CAP_MAX_DEPTH = 255, 64
+CAP_KINDS = ["chain", "bushy", "bushy128", "bushy129", "both"]
+CAP_VARIANTS = ["normal", "linear", "mix", "probit", "categorical_k3", "categorical_k5", "normal_p100", "normal_p128",
+                "upstream", "categorical_k12_linear"]
+CAP_ROWS = {"chain": 1000, "bushy": 300, "bushy128": 128, "bushy129": 129, "both": 2000}
+# every (kind, variant) of the matrix.  Not on the pure one-hot column (chain): probit, which leaves only the stump
+# there.  Under compat = 3 index 254 of every full tree on that column is an EMPTY right leaf, so chain / upstream is
+# held to full trees with leaves that would still split (cap_targets: "full"); the column next to a continuous one,
+# kind "both", ends full trees in a leaf that holds rows.  The two smallest row counts that can fill 255 nodes run
+# the Normal family and the unrolled K-vector instance.
+# K = 12 with linear leaves (three tiles of the run-time-K instances): two classes carry the signal, at logits of
+# +-4 f, the other ten sit at -3 -- with a signal spread over all classes the accepted trees stay stumps.
+ALL_CAPS = ([("chain", v) for v in CAP_VARIANTS if v != "probit"] + [("bushy", v) for v in CAP_VARIANTS]
+            + [(k, v) for k in ("bushy128", "bushy129") for v in ("normal", "categorical_k3")]
+            + [("both", v) for v in CAP_VARIANTS])
+# (kind, variant) -> the first seed whose oracle run meets check_cap_reach, where seed 0 does not
+CAP_SEEDS = {("both", "normal"): 3, ("both", "probit"): 9, ("both", "categorical_k5"): 14, ("both", "normal_p128"): 1}
+
+
+def cap_targets(kind, variant):
+    """(node cap, depth cap, dropped rows): the limits a case exists for.  Under compat = 3 an empty right leaf of a
+    one-hot split grows, so the one-hot column fills the node table long before depth 64: that variant is held to the
+    node cap alone -- on the pure one-hot column to "full": a 255-node tree with leaves that would still split, whose
+    last node is an empty leaf."""
+    node = kind != "chain" or (variant == "upstream" and "full")
+    depth = kind in ("chain", "both") and variant != "upstream"
+    return node, depth, kind == "both"
+
+
+def cap_case(kind, variant, seed):
+    """m = 2 trees (one for the 100 / 128 particle variants, except on "both": with a single tree none of 32 keys
+    reaches depth 64 there), all re-sampled at every step, 8 steps of which 4 tune,
+    alpha = 0.9999, beta = 0: P(split) = 0.9999 at every depth below 64.
+    chain: one one-hot column of 100 codes -- every split peels one code off to the left, the rest goes right.
+    bushy*: two continuous columns, 300 / 128 / 129 rows.
+    both: the one-hot column (split prior 20, 10 % missing) next to a continuous column, 2000 rows."""
+    rng = np.random.default_rng([CAP_KINDS.index(kind), CAP_VARIANTS.index(variant), int(seed)])
+    n = CAP_ROWS[kind]
+    if kind == "chain":
+        code = rng.integers(0, 100, n).astype(float)
+        X, rules, prior = code[:, None], np.array([1], np.int32), np.ones(1)
+        f = np.sin(0.7 * code) + 0.02 * code
+    elif kind.startswith("bushy"):
+        X, rules, prior = rng.normal(size=(n, 2)), np.zeros(2, np.int32), np.ones(2)
+        f = np.sin(3 * X[:, 0]) + np.where(X[:, 1] < 0, X[:, 1], -0.5 * X[:, 1])
+    elif kind == "both":
+        code = rng.integers(0, 100, n).astype(float)
+        f = np.sin(0.7 * code) + 0.02 * code
+        code[rng.random(n) < 0.1] = np.nan
+        z = rng.normal(size=n)
+        X, rules, prior = np.stack([code, z], axis=1), np.array([1, 0], np.int32), np.array([20.0, 1.0])
+        f = np.where(np.isnan(code), 0.0, f) + np.where(z < 0, z, -0.5 * z)
+    else:
+        raise KeyError(kind)
+    c = dict(name=f"cap/{kind}/{variant}", kind=kind, variant=variant, m=2, P=10, steps=8, batch=(1.0, 1.0), rules=rules,
+             prior=prior, seed=2000 + int(seed), alpha=0.9999, beta=0.0, X=X)
+    if variant in ("normal", "linear", "mix", "normal_p100", "normal_p128", "upstream"):
+        c.update(Y=f + rng.normal(0, 0.3, n))
+        if variant in ("linear", "mix"):
+            c.update(response=variant)
+        elif variant == "normal_p100":
+            c.update(P=100, m=2 if kind == "both" else 1)
+        elif variant == "normal_p128":
+            c.update(P=128, m=2 if kind == "both" else 1)
+        elif variant == "upstream":
+            c.update(compat=3)
+    elif variant == "probit":
+        from scipy.special import ndtr
+        c.update(Y=(rng.random(n) < ndtr(2.0 * f)).astype(float), family="bernoulli_probit")
+    elif variant in ("categorical_k3", "categorical_k5"):
+        K = int(variant[-1])
+        logits = np.stack([2.0 * f * (k - 0.5 * (K - 1)) for k in range(K)]) + rng.gumbel(size=(K, n))
+        c.update(Y=np.argmax(logits, axis=0).astype(float), family="categorical", K=K)
+    elif variant == "categorical_k12_linear":
+        logits = np.full((12, n), -3.0)
+        logits[0], logits[1] = 4.0 * f, -4.0 * f
+        logits += rng.gumbel(size=(12, n))
+        c.update(Y=np.argmax(logits, axis=0).astype(float), family="categorical", K=12, response="linear")
+    else:
+        raise KeyError(variant)
+    return c
+
+
+def make_cap(kind, variant):
+    return cap_case(kind, variant, CAP_SEEDS.get((kind, variant), 0))
+
+
+def tree_depths(left, right, var):
+    """Depth of every node of one tree (tree-local child indices), by a walk from the root."""
+    depth = np.full(len(var), -1, np.int64)
+    todo = [(0, 0)]
+    while todo:
+        k, d = todo.pop()
+        assert depth[k] < 0, "a node is reached twice"
+        depth[k] = d
+        if var[k] >= 0:
+            todo += [(int(left[k]), d + 1), (int(right[k]), d + 1)]
+    assert (depth >= 0).all(), "a node is not reached from the root"
+    return depth
+
+
+def step_trees(c, packed):
+    """The trees of one entry of run_case's `trees` (the arrays of a step's export_trees(0), concatenated) as
+    (var, left, right, count) per tree.  Every tree is re-sampled at every step: the batch holds m trees."""
+    m = c["m"]
+    packed = np.asarray(packed)
+    off = packed[m: 2 * m + 1].astype(np.int64)
+    assert off[0] == 0 and np.array_equal(np.sort(packed[:m]), np.arange(m)), "not a batch of all m trees"
+    N = int(off[-1])
+    var, left, right, count = (packed[2 * m + 1 + k * N: 2 * m + 1 + (k + 1) * N].astype(np.int64) for k in range(4))
+    return [(var[a:b], left[a:b], right[a:b], count[a:b]) for a, b in zip(off[:-1], off[1:])]
+
+
+def forest_trees(forest):
+    off = np.asarray(forest.node_off, np.int64)
+    return [tuple(np.asarray(getattr(forest, f))[a:b].astype(np.int64) for f in ("var", "left", "right", "count"))
+            for a, b in zip(off[:-1], off[1:])]
+
+
+def tree_at_caps(tree, n):
+    """What one exported tree says about the two limits."""
+    var, left, right, count = tree
+    depth = tree_depths(left, right, var)
+    leaf = var < 0
+    full = len(var) == CAP_MAX_NODES
+    return dict(nodes=len(var), depth=int(depth.max()),
+                # the last node index is a live leaf, and growth was still wanted: the cap is what stopped it
+                node_cap=bool(full and leaf[-1] and count[-1] > 0 and (leaf & (depth < CAP_MAX_DEPTH) & (count >= 2)).any()),
+                depth_cap=bool((leaf & (depth == CAP_MAX_DEPTH) & (count >= 2)).any()),
+                full_open=bool(full and (leaf & (depth < CAP_MAX_DEPTH) & (count >= 2)).any()),
+                dropped=bool(full and count[leaf].sum() < n),
+                open_leaves=int((leaf & (depth < CAP_MAX_DEPTH) & (count >= 2)).sum()),
+                held_at_depth=int((leaf & (depth == CAP_MAX_DEPTH) & (count >= 2)).sum()),
+                empty_leaves=int((leaf & (count == 0)).sum()))
+
+
+def cap_reach(c, res):
+    """What a run of a cap case reached, from its exports alone (every step's accepted batch, not only the final
+    forest): see check_cap_reach.  `first_full`: the first step after which a tree at a limit is stored (`first_deep`: at the depth limit)."""
+    n = c["X"].shape[0]
+    stats, first_full, first_deep = [], None, None
+    for it, packed in enumerate(res["trees"]):
+        for t in step_trees(c, packed):
+            s = tree_at_caps(t, n)
+            stats.append(s)
+            if first_full is None and (s["full_open"] or s["depth_cap"]):
+                first_full = it
+            if first_deep is None and s["depth_cap"]:
+                first_deep = it
+    st0 = PyBartSettings.from_data(c["X"], c.get("bart_Y", c["Y"]), m=c["m"], num_particles=c["P"])
+    return dict(max_nodes=max(s["nodes"] for s in stats), max_depth=max(s["depth"] for s in stats),
+                node_cap=sum(s["node_cap"] for s in stats), full_open=sum(s["full_open"] for s in stats), depth_cap=sum(s["depth_cap"] for s in stats),
+                dropped=sum(s["dropped"] for s in stats), both_in_one_tree=sum(s["node_cap"] and s["depth_cap"] for s in stats),
+                open_leaves=max(s["open_leaves"] for s in stats), held_at_depth=max(s["held_at_depth"] for s in stats),
+                empty_leaves=max(s["empty_leaves"] for s in stats), first_full=first_full, first_deep=first_deep,
+                saturations=int(res["counters"]["saturations"]),
+                leaf_sd_tuned=bool(np.any(np.asarray(res["state"]["leaf_sd"]) != st0.init_leaf_sd)))
+
+
+def cap_prefix(c, steps):
+    """The first `steps` steps of the case, tuning as the whole run tunes."""
+    return dict(c, steps=int(steps), tune_steps=c["steps"] // 2)
+
+
+def check_cap_reach(c, res):
+    """The conditions a cap case exists for (no pytest here: the golden generator calls it too)."""
+    r = cap_reach(c, res)
+    node, depth, dropped = cap_targets(c["kind"], c["variant"])
+    assert not node or r["full_open" if node == "full" else "node_cap"] > 0, \
+        f"{c['name']}: no accepted tree is stopped by the node cap: {r}"
+    assert not depth or r["depth_cap"] > 0, f"{c['name']}: no accepted tree holds rows in a leaf at depth 64: {r}"
+    assert not dropped or r["dropped"] > 0, f"{c['name']}: no 255-node tree has dropped rows: {r}"
+    assert r["saturations"] == 0, f"{c['name']}: fixed-point saturation: {r}"
+    assert r["leaf_sd_tuned"], f"{c['name']}: tuning did not change leaf_sd: {r}"
+    return r

@@ -261,9 +261,10 @@ def test_both_library_builds_export_the_entry_point(so):
 
 def test_the_abi_header_is_untouched():
     """The entry point lives in include/pgbart_pointwise.h: pgbart.h -- what every backend exports in full -- is the
-    parent's, byte for byte."""
+    parent's, byte for byte.  (Re-pinned once since: its Limits comment now names the tests that hold the two limits on
+    tree size; no declaration moved.)"""
     with open(os.path.join(ROOT, "include", "pgbart.h"), "rb") as fh:
-        assert hashlib.sha256(fh.read()).hexdigest() == "1438ebfdba4e67d3595bd7ff8b25485cb547111e5683d879cfac8cb961830fc7"
+        assert hashlib.sha256(fh.read()).hexdigest() == "042089e8cc3a88ac9b377eca54e71c05fe13b1bb1cd3945078f83a4568a96307"
     from pymc_bart_amd import _abi
 
     assert "pgb_pointwise_loglik" not in _abi.SYMBOLS

@@ -20,8 +20,10 @@ struct Fin {  // result of finishing the pending split of an old particle (kept 
 // defines (pgb_scan64 / pgb_weights_scan / pgb_pick in include/pgbart_spec.h).
 // NH = PGB_MAX_PARTICLES / 64 particles per lane: lane l holds the log-weights of particles l, l + 64, ...; the
 // cumulative weights are one DPP scan per block of 64, each later block shifted by the total of the block before.
+// wave_weights: the scan (W, every lane its particles' cumulative weights) and its total; wave_pick_from: the pick
+// for ONE offset u from that scan; wave_pick: both.
 template <int NH>
-__device__ __forceinline__ int wave_pick(const double (&lw)[NH], int first, int cnt, double u) {
+__device__ __forceinline__ double wave_weights(const double (&lw)[NH], int first, int cnt, double (&W)[NH], double (&w)[NH]) {
   const int lane = threadIdx.x & 63;
   bool act[NH];
   double m = -1.0e308;
@@ -32,7 +34,6 @@ __device__ __forceinline__ int wave_pick(const double (&lw)[NH], int first, int 
     if (act[hq] && lw[hq] > m) m = lw[hq];  // (a maximum: any order)
   }
   const double mx = wave_max_d(m);
-  double W[NH];
 #define PGB_SCAN_STEP(ctrl, rm)                                                       \
   {                                                                                   \
     const int tl = __builtin_amdgcn_update_dpp(0, __double2loint(Wh), ctrl, rm, 0xf, 0); \
@@ -43,6 +44,7 @@ __device__ __forceinline__ int wave_pick(const double (&lw)[NH], int first, int 
 #pragma unroll
   for (int hq = 0; hq < NH; ++hq) {
     double Wh = act[hq] ? pgb_exp(lw[hq] - mx) + 1e-12 : 0.0;
+    w[hq] = Wh;  // (the particle's own weight, before the scan)
     PGB_SCAN_STEP(0x111, 0xf)  // row_shr:1
     PGB_SCAN_STEP(0x112, 0xf)  // row_shr:2
     PGB_SCAN_STEP(0x114, 0xf)  // row_shr:4
@@ -59,15 +61,27 @@ __device__ __forceinline__ int wave_pick(const double (&lw)[NH], int first, int 
 #pragma unroll
   for (int hq = 0; hq < NH; ++hq)
     if ((last >> 6) == hq) tot = readlane_d(W[hq], last & 63);  // (wave-uniform)
+  return tot;
+}
+template <int NH>
+__device__ __forceinline__ int wave_pick_from(const double (&W)[NH], double tot, int first, int cnt, double u) {
+  const int lane = threadIdx.x & 63;
+  const int last = first + cnt - 1;
   const double thr = u * tot;
 #pragma unroll
   for (int hq = 0; hq < NH; ++hq) {
     const int q = lane + 64 * hq;
-    const bool hit = act[hq] && (q < last) && !(thr > W[hq]);
+    const bool hit = (q >= first) && (q < last) && !(thr > W[hq]);
     const unsigned long long mk = __ballot(hit);
     if (mk) return 64 * hq + (int)__ffsll((long long)mk) - 1;
   }
   return last;
+}
+template <int NH>
+__device__ __forceinline__ int wave_pick(const double (&lw)[NH], int first, int cnt, double u) {
+  double W[NH], w[NH];
+  const double tot = wave_weights<NH>(lw, first, cnt, W, w);
+  return wave_pick_from<NH>(W, tot, first, cnt, u);
 }
 
 // [U] SampleSplittingVariable.rvs on one wave, from stored prefix sums (pgb_sample_var)
@@ -761,10 +775,214 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
       }
       stop = __ballot(pend_any) == 0ull;
       int pick;
+      bool fold = false;
+      int sel_fold = 0, pop_fold = 0;
       if (!stop) {
         // [U] systematic resampling of particles 1..P-1: ancestor of new particle p
         const double ui = (u_res + (double)(p - 1)) / (double)Lc;
-        pick = wave_pick<NH>(lwv, 1, Lc, ui);
+        double W[NH], wv[NH];
+        const double tot = wave_weights<NH>(lwv, 1, Lc, W, wv);
+        pick = wave_pick_from<NH>(W, tot, 1, Lc, ui);
+        if constexpr (!MK && !LIN) {
+        if (S.fold_last) {
+          // ---- Is round r, which this slot is about to propose, EMPTY AND FINAL?  That is: no new particle i = 1..P-1
+          // attempts a split, and none has a node left after its pop.  Then the next slot would find nothing pending
+          // and end the tree; this slot does so itself (below) and the empty round costs no slot.
+          // Every workgroup decides this on its wave 0, from the same words with the same instructions: the control
+          // word (round, iter, u_res, u_fin, inv_sigma2, sse0, lid_gen), the job records, split statistics and
+          // log-likelihood sums of the previous slot, the previous FINAL/INIT sums (ia), the nodes the old particles
+          // would pop (OT[q].nd[next_pop]), S.prior_leaf and the scalars of the argument block.  Nothing that differs
+          // between workgroups (p, b) enters it.
+          // A new particle whose ancestor has two or more nodes left keeps one after its pop, so the round is not final.
+          const int last = Lc;
+          int remv[NH];  // nodes the lane's old particles have left to pop (their records are in LDS, written by this lane)
+#pragma unroll
+          for (int hq = 0; hq < NH; ++hq)
+            remv[hq] = ispv[hq] ? s_fin[tid + 64 * hq].n_nodes - s_fin[tid + 64 * hq].next_pop : 0;
+          // (1) What nearly every slot that is not a tree's last but one ends on, in a handful of instructions: an old
+          // particle with two or more nodes left whose own weight exceeds the spacing tot / Lc of the resampling
+          // thresholds is an ancestor whatever u_res is -- its stretch (max W[< q], W[q]] of the cumulative weights is
+          // longer than the distance of two neighbouring thresholds, the rounding of the scan and of the thresholds
+          // (a few ulp of tot) being far inside the margin of 2^-20.  This only ever rules a fold OUT where there is
+          // none; what it lets through is decided exactly below.
+          bool can = true;
+          {
+            bool heavy = false;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) heavy = heavy || (remv[hq] >= 2 && wv[hq] * (double)Lc >= (1.0 + 1.0 / 1048576.0) * tot);
+            if (__ballot(heavy) != 0ull) can = false;
+          }
+          // (2) Lane i <-> new particle i.  Its ancestor a_i is pgb_pick's: the first q in [1, Lc) with
+          // !(thr_i > W[q]), thr_i = ((u_res + (i - 1)) / Lc) * tot, else Lc -- the comparison of wave_pick_from.  The
+          // scan W is not bitwise monotone, its running maximum M is, and the first q with !(thr > W[q]) is the first
+          // q with !(thr > M[q]) (M[q] reaches thr exactly when some W[q' <= q] does): a bisection of M per lane,
+          // ceil(log2 Lc) ds_bpermute steps, gives pgb_pick's ancestor for every i at once.  (A NaN among the weights
+          // -- which max() would drop and the comparison would not -- leaves the slot unfolded.)
+          int av[NH];
+          if (can) {
+            bool nanw = false;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) nanw = nanw || (tid + 64 * hq >= 1 && tid + 64 * hq <= last && W[hq] != W[hq]);
+            if (__ballot(nanw) != 0ull) can = false;
+          }
+          if (can) {
+            double thr[NH];
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) thr[hq] = ((u_res + (double)(tid + 64 * hq - 1)) / (double)Lc) * tot;
+            // (2a) one particle D holds more than half of the weight (n in the tens of thousands: nearly always).  The
+            // thresholds rise with i (every operation of thr_i is monotone), so if the lowest, thr_1, lies above every
+            // W[q < D] and the highest, thr_Lc, does not lie above W[D], then D is the ancestor of EVERY new particle.
+            bool single = false;
+            int D = 0;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              const int q = tid + 64 * hq;
+              const unsigned long long dm = __ballot(q >= 1 && q <= last && wv[hq] * 2.0 > tot);
+              if (dm != 0ull) D = 64 * hq + (int)__ffsll((long long)dm) - 1;  // (at most one lane in all)
+            }
+            if (D >= 1) {
+              const double t1 = readlane_d(thr[0], 1);
+              double tL = 0.0, WD = 0.0;
+#pragma unroll
+              for (int hq = 0; hq < NH; ++hq) {
+                if ((Lc >> 6) == hq) tL = readlane_d(thr[hq], Lc & 63);
+                if ((D >> 6) == hq) WD = readlane_d(W[hq], D & 63);
+              }
+              bool below = false;
+#pragma unroll
+              for (int hq = 0; hq < NH; ++hq) {
+                const int q = tid + 64 * hq;
+                below = below || (q >= 1 && q < D && q < last && !(t1 > W[hq]));
+              }
+              single = __ballot(below) == 0ull && (D == last || !(tL > WD));
+            }
+            if (single) {
+              int rD = 0;
+#pragma unroll
+              for (int hq = 0; hq < NH; ++hq) {
+                av[hq] = D;
+                if ((D >> 6) == hq) rD = __builtin_amdgcn_readlane(remv[hq], D & 63);
+              }
+              if (rD >= 2) can = false;
+            } else {
+            // (2b) the general case
+            double M[NH];
+#define PGB_MAX_STEP(ctrl, rm)                                                        \
+  {                                                                                   \
+    const int tl = __builtin_amdgcn_update_dpp(0, __double2loint(Mh), ctrl, rm, 0xf, 0); \
+    const int th = __builtin_amdgcn_update_dpp(0, __double2hiint(Mh), ctrl, rm, 0xf, 0); \
+    Mh = fmax(Mh, __hiloint2double(th, tl)); /* (W >= 0: the 0 a lane without a source reads changes nothing) */ \
+  }
+            double carry = 0.0;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              double Mh = W[hq];
+              PGB_MAX_STEP(0x111, 0xf)  // row_shr:1
+              PGB_MAX_STEP(0x112, 0xf)  // row_shr:2
+              PGB_MAX_STEP(0x114, 0xf)  // row_shr:4
+              PGB_MAX_STEP(0x118, 0xf)  // row_shr:8
+              PGB_MAX_STEP(0x142, 0xa)  // row_bcast:15 -> rows 1, 3
+              PGB_MAX_STEP(0x143, 0xc)  // row_bcast:31 -> rows 2, 3
+              if (hq > 0) Mh = fmax(Mh, carry);
+              if (hq + 1 < NH) carry = readlane_d(Mh, 63);
+              M[hq] = Mh;
+            }
+#undef PGB_MAX_STEP
+            const int steps = 32 - __clz(last - 1);  // 2^steps >= last (wave-uniform; 0 for one particle)
+            bool keeps = false;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              const int i = tid + 64 * hq;
+              int lo = 1, hi = last;  // the answer lies in [lo, hi]; hi == last: none below it
+              for (int st = 0; st < steps; ++st) {
+                const int mid = (lo + hi) >> 1;  // (< last while lo < hi)
+                double v = 0.0;
+#pragma unroll
+                for (int h2 = 0; h2 < NH; ++h2) {
+                  const double t = __shfl(M[h2], mid & 63);
+                  if ((mid >> 6) == h2) v = t;
+                }
+                if (lo < hi) {
+                  if (!(thr[hq] > v)) hi = mid;
+                  else lo = mid + 1;
+                }
+              }
+              av[hq] = lo;
+              int ra = 0;
+#pragma unroll
+              for (int h2 = 0; h2 < NH; ++h2) {
+                const int t = __shfl(remv[h2], lo & 63);
+                if ((lo >> 6) == h2) ra = t;
+              }
+              keeps = keeps || (i >= 1 && i < P && ra >= 2);
+            }
+            if (__ballot(keeps) != 0ull) can = false;
+            }
+          }
+          if (can) {
+            // every ancestor has at most one node left.  Lane q: the depth of the node old particle q would pop if
+            // that node can be split at all (-1: nothing to pop, the tree is full, fewer than two rows, or too deep:
+            // P(leaf) = 1 there and the coin is < 1) -- the tests of the proposal below, on the same node.
+            int dq[NH];
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              dq[hq] = -1;
+              if (ispv[hq] && remv[hq] >= 1) {
+                const Fin& f = s_fin[tid + 64 * hq];
+                int d, cnt;
+                if (f.next_pop < f.nn_old) {
+                  d = popv[hq].depth;
+                  cnt = popv[hq].cnt;
+                } else {
+                  d = f.depth + 1;
+                  cnt = f.next_pop == f.nn_old ? f.cL : f.cR;
+                }
+                if (f.n_nodes + 2 <= MAXN && cnt >= 2 && d < PGB_MAX_DEPTH) dq[hq] = d;
+              }
+            }
+            bool att = false;
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              const int i = tid + 64 * hq;
+              const bool valid = i >= 1 && i < P;
+              const int a = av[hq];
+              int da = -1, ra = 0;
+#pragma unroll
+              for (int h2 = 0; h2 < NH; ++h2) {
+                const int t = __shfl(dq[h2], a & 63), t2 = __shfl(remv[h2], a & 63);
+                if ((a >> 6) == h2) da = t, ra = t2;
+              }
+              if (valid && da >= 0) {
+                // the coin of new particle i: (iter, r, i, PROPOSE, 0).u0, what s_pre[0][0] holds for i = p
+                const double u_i = pgb_draw2(S.seed, it, (uint32_t)r, (uint32_t)i, PGB_RNG_PROPOSE, 0).u0;
+                att = att || (S.prior_leaf[da] < u_i);
+              }
+              pop_fold += __popcll(__ballot(valid && ra >= 1));
+            }
+            fold = __ballot(att) == 0ull;
+          }
+          if (fold) {
+            // [U] get_particle_tree, one slot early: new particle i carries lw[a_i] -- the next slot would compute
+            // the very same double from the header fields this slot copies from a_i -- and lane 0 the reference
+            // particle's weight
+            double lwn[NH];
+#pragma unroll
+            for (int hq = 0; hq < NH; ++hq) {
+              const int i = tid + 64 * hq;
+              const int a = av[hq];
+              double g = 0.0;
+#pragma unroll
+              for (int h2 = 0; h2 < NH; ++h2) {
+                const double t = __shfl(lwv[h2], a & 63);
+                if ((a >> 6) == h2) g = t;
+              }
+              lwn[hq] = (i >= 1 && i < P) ? g : 0.0;
+            }
+            if (tid == 0) lwn[0] = normal ? sse0 * (-0.5 * c.inv_sigma2) : sse0;
+            sel_fold = wave_pick<NH>(lwn, 0, P, c.u_fin);
+          }
+        }
+        }
       } else {
         // [U] get_particle_tree: final choice among all P particles (lane 0 = reference particle)
         if (tid == 0) lwv[0] = normal ? sse0 * (-0.5 * c.inv_sigma2) : sse0;
@@ -777,8 +995,13 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
         if (ispv[hq]) s_pop[tid + 64 * hq] = popv[hq];
       pick0 = pick;
       if (tid == 0) {
-        s_i[0] = stop ? 1 : 0;
-        s_i[1] = pick;
+        // [0]: the slot ends the tree (bit 0: nothing was pending; bit 1: folded -- the round it would propose is
+        // empty and final); [1]: whose table new particle p copies; [2]: the final choice
+        s_i[0] = (stop ? 1 : 0) | (fold ? 2 : 0);
+        s_i[1] = stop ? p : pick;  // (no resampling in a slot that found nothing pending: particle p finishes itself)
+        s_i[2] = stop ? pick : sel_fold;
+        // the particle steps of the folded round (its pops), which the next slot would have counted
+        if (fold && b == 0 && pop_fold) atomicAdd(&S.counters[0], (unsigned long long)pop_fold);
       }
     }
 #if PGB_CTRL_FINX
@@ -834,13 +1057,14 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
     }
 #endif
     __syncthreads();
+    // A folded slot goes on as the slot that ends the tree: round r is complete without a row pass, and new particle p
+    // is its ancestor with the pending split applied (below).  The labels of the accepted particle stay where its
+    // ancestor's are (F.loc_gen): never the generation dst_gen = lid_gen + 1 that this slot's row pass writes the fresh
+    // stumps to, because the previous slot (dst_gen = lid_gen) moved every particle whose labels were in lid_gen + 1
+    // forward (Job::copy), and a split writes to lid_gen.  The refresh round r would have made for a particle in
+    // lid_gen + 2 is not needed: nothing writes that generation before the tree is stored.
     stop = s_i[0] != 0;
-    if (stop) {
-      sel = s_i[1];
-      anc = p;  // no resampling in the final slot: particle p finishes itself
-    } else {
-      anc = s_i[1];
-    }
+    anc = s_i[1];
     TR(3);
     // -------- new particle p := old particle anc with its pending split applied (all threads)
     {
@@ -1083,7 +1307,10 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
   int lower_next = c.lower, k_next = c.k, batch_next = c.batch_n;
   bool more = true;
   if (stop) {
-    const Fin& F = s_fin[p];
+    const Fin& F = s_fin[anc];  // (anc == p unless the slot is folded)
+    sel = s_i[2];
+    // (whether the slot is folded is read from s_i[0] by the one lane that needs it, where it needs it: this instance
+    //  has no scalar register to spare for a flag that lives across the block)
     __syncthreads();  // the node copy above is complete (this workgroup reads it back below)
     const int tree_old = c.lower + c.k;
     more = (c.k + 1 < c.batch_n);
@@ -1105,7 +1332,7 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
     if (tid == 0) {  // particle header (kept for inspection / export)
       me->n_nodes = F.n_nodes;
       me->n_leaves = F.n_leaves;
-      me->next_pop = F.next_pop;
+      me->next_pop = F.next_pop + (((s_i[0] & 2) && F.next_pop < F.n_nodes) ? 1 : 0);  // folded: the pop of the empty round
       me->loc_gen = F.loc_gen;
       me->loc_slot = F.loc_slot;
       me->sse_tot = F.sse_tot;
@@ -1234,7 +1461,7 @@ void k_ctrl(const Dev* __restrict__ Sp, int par, int nwg, Ctrl* __restrict__ ctr
       cmd->tune = c.tune;
       cmd->rs_count = c.rs_count + (c.tune ? 1 : 0);
       atomicAdd(&S.counters[1], 1ull);
-      atomicAdd(&S.counters[3], 1ull);
+      atomicAdd(&S.counters[3], (s_i[0] & 2) ? 2ull : 1ull);  // (folded: round r - 1 and the empty round r)
     }
     if (!has_init) {  // last tree of the last requested step
       if (b == 0 && tid == 0) {

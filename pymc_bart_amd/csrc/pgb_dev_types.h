@@ -248,7 +248,10 @@ struct DevT {  // kernel argument block (by value)
   // k_rows_mk<.., F32>): nchunks rounded up to 8 counts, so that a lane's sixteen counts are two aligned 16-byte loads
   // (select_split_row<V16>).  Every other instance strides by nchunks, as before.  (At the END of the block: the
   // instances that do not use it keep every offset -- and with it their register allocation -- as it was.)
-  int32_t cc_stride, pad_cc;
+  int32_t cc_stride;
+  // PGB_FOLD_LAST (default 1): a slot whose proposed round is empty and final ends the tree itself (k_ctrl); 0: the
+  // next slot does.  Same results either way, one slot per tree apart.  (Takes the padding: no offset moves.)
+  int32_t fold_last;
 };
 typedef DevT<false> Dev;   // as the host fills it in and the kernels receive it
 typedef DevT<true> DevG;   // as the kernels read it (see above)

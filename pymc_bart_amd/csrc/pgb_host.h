@@ -295,6 +295,12 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   d.nchunks = (int)((s->n + CH - 1) / CH);
   d.n_pad = (long long)d.nchunks * CH;
   d.cc_stride = (d.nchunks + 7) & ~7;
+  // PGB_FOLD_LAST (default 1; 0 = off): a slot whose proposed SMC round is empty and final ends the tree itself instead
+  // of leaving that to the next slot (k_ctrl, single-output constant-leaf models).  Results are identical either way;
+  // only pgb_counters.slots differs, by one per tree update that folds.  Read here, per handle, so that two samplers
+  // of one process can run the two paths side by side.
+  d.fold_last = 1;
+  if (const char* e = getenv("PGB_FOLD_LAST")) d.fold_last = atoi(e) != 0 ? 1 : 0;
   d.p = s->p;
   d.m = s->m;
   d.P = s->num_particles;

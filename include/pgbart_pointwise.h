@@ -56,6 +56,25 @@ int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t* forest_tre
  * written.  HIP library only (both particle builds). */
 int pgb_psis_rows(const double* ll_dev, int32_t D, int64_t n_rows, int64_t ld, int32_t tail_len, double* out_dev,
                   void* stream);
+
+/* PSIS-weighted expectations over the same weights (pgbart_psis.h: pgb_psis_row_expect): per row the self-normalised
+ * sum of a functional of a second matrix g_dev [D][ldg] -- the draws' predictors or replicated observations of the
+ * same rows (the first n_rows of every ldg are read) -- under the row's Pareto-smoothed weights, which never leave the
+ * kernel.  ll_dev, D, n_rows, ld, tail_len: as pgb_psis_rows takes them.  ldg is separate from ld, so that output k of
+ * pgb_predict's [D][K][nb] can be passed as g_dev + k * nb with ldg = K * nb.
+ *   kind     PGB_PSIS_G_VALUE (0): E[g] and E[g^2] (n_e = 2);  PGB_PSIS_G_PIT (1): the mid-p LOO-PIT of y_dev
+ *            [n_rows], E[(g < y) + 0.5 (g == y)] (n_e = 1).  y_dev is not read for kind 0 (may be NULL)
+ *   out_dev  [2 + n_e][n_rows] = (elpd_loo_i, k_i, E_0[, E_1]); the first two are pgb_psis_rows' bits
+ * g is held within +-1e150 (a NaN becomes -1e150).  Everything is validated before the launch: PGB_E_INVALID for what
+ * pgb_psis_rows refuses, a NULL g_dev, ldg < n_rows, a kind other than 0 / 1, a NULL y_dev with kind 1.  The call
+ * returns when the output is written.  HIP library only (both particle builds). */
+int pgb_psis_expect(const double* ll_dev, int32_t D, int64_t n_rows, int64_t ld, int32_t tail_len, const double* g_dev,
+                    int64_t ldg, const double* y_dev, int32_t kind, double* out_dev /* [2 + n_e][n_rows] */, void* stream);
+
+/* a[d][k][i] = a[d][k][i] + offset[k][i] in place: pgb_predict's [D][K][n_rows] made the linear predictor that
+ * pgb_pointwise_loglik and pgb_ppc_draw see (one rounding per element, so the host's mu + offset bit for bit).
+ * PGB_E_INVALID for a NULL pointer or D, K, n_rows < 1.  HIP library only (both particle builds). */
+int pgb_add_offset(double* a_dev, int32_t D, int32_t K, int64_t n_rows, const double* offset_dev, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,21 @@
  * same bits on both sides (its arguments are ratios of integers below 2 PGB_PSIS_MAX_TAIL; within 1 ulp of sqrt).
  * log1p / expm1: pgb_psis_log1p corrects log(1 + x) by x / ((1 + x) - 1); pgb_psis_expm1 is a Taylor polynomial for
  * |y| < 1/4 (where exp(y) - 1 cancels) and exp(y) - 1 beyond.
+ *
+ * PSIS-weighted expectations (pgb_psis_row_expect; pgb_psis_expect, include/pgbart_pointwise.h): a second row
+ * g[0 .. D-1] of the same draws (a predictor, a replicated observation) and the self-normalised sum
+ * sum_d exp(w_d) g_c(d) / sum_d exp(w_d) over the row's smoothed weights, which never leave the row.  With mx, cutoff, T,
+ * the final tail weights w_t (ascending), wmax, Dn (the N of the denominator above) and St (its S) exactly as above:
+ *
+ *   clamp     v_d = pgb_psis_gclamp(g_d): held within +-PGB_PSIS_G_MAX = 1e150, so that squares and sums of
+ *             PGB_PSIS_MAX_DRAWS terms stay finite; a NaN becomes -PGB_PSIS_G_MAX
+ *   kind      PGB_PSIS_G_VALUE (0): g_0 = v, g_1 = v v -- two outputs, E[g] and E[g^2]
+ *             PGB_PSIS_G_PIT   (1): g_0 = (v < y) + 0.5 (v == y), y the row's observed value (pgb_ppc_compare's sense:
+ *             the mid-p LOO-PIT) -- one output; y is not read for kind 0
+ *   result    E_c = (Gn_c e + Gt_c) / (Dn e + St), e = exp(cutoff - wmax): Gn_c the LANE SUM over the draws outside the
+ *             tail (numbered by draw index) of pgb_psis_den_term(x_d, cutoff) g_c(d), Gt_c the LANE SUM over the tail
+ *             in ascending order of exp(w_t - wmax) g_c(idx_t).  In both the product is formed first, then added (no
+ *             FMA), so that g = 1 gives exactly 1.
  */
 #ifndef PGBART_PSIS_H
 #define PGBART_PSIS_H
@@ -175,20 +190,38 @@ PGB_HD double pgb_psis_elpd(double Nn, double Dn, double Vt, double St, double m
   return (vmax + pgb_log_t(num, tb->logt)) - (wmax + pgb_log_t(den, tb->logt));
 }
 
+/* the functionals of the PSIS-weighted expectations */
+#define PGB_PSIS_G_VALUE 0
+#define PGB_PSIS_G_PIT 1
+#define PGB_PSIS_G_NONE (-1) /* (pgb_psis_row: no second row) */
+#define PGB_PSIS_G_MAX 1e150
+PGB_HD double pgb_psis_gclamp(double g) { return g > PGB_PSIS_G_MAX ? PGB_PSIS_G_MAX : (g >= -PGB_PSIS_G_MAX ? g : -PGB_PSIS_G_MAX); }
+PGB_HD int pgb_psis_n_expect(int kind) { return kind == PGB_PSIS_G_VALUE ? 2 : 1; }
+/* g_0 of the clamped value v */
+PGB_HD double pgb_psis_g0(double v, double y, int kind) {
+  return kind == PGB_PSIS_G_PIT ? (v < y ? 1.0 : 0.0) + 0.5 * (v == y ? 1.0 : 0.0) : v;
+}
+/* E_c from its two lane sums and the denominator's */
+PGB_HD double pgb_psis_ratio(double Gn, double Gt, double Dn, double St, double cutoff, double wmax, const pgb_lltabs* tb) {
+  const double e = pgb_exp_t(cutoff - wmax, tb->expt);
+  return (Gn * e + Gt) / (Dn * e + St);
+}
+
 /* doubles / int32s of workspace pgb_psis_row needs */
 #define PGB_PSIS_WORK_DOUBLES(M) (2 * ((M) + 1) + 3 * PGB_PSIS_LANES)
 #define PGB_PSIS_WORK_INTS(M) ((M) + 1)
 
-/* The whole of one row, ll[d * stride], d < D: out2 = (elpd_loo_i, k_i) -- what the device kernel computes.  The
- * caller has checked D, M (above) and provides the workspace. */
-PGB_HD void pgb_psis_row(const double* ll, int64_t stride, int D, int M, const pgb_lltabs* tb, double* wk, int32_t* idx,
-                         double* out2) {
+/* The whole of one row, ll[d * stride], d < D, with the second row g[d * gstride] when kind is not PGB_PSIS_G_NONE:
+ * out = (elpd_loo_i, k_i[, E_0[, E_1]]) -- what the device kernels compute.  The caller has checked D, M (above) and
+ * provides the workspace. */
+PGB_HD void pgb_psis_row_any(const double* ll, int64_t stride, const double* g, int64_t gstride, double y, int kind, int D,
+                             int M, const pgb_lltabs* tb, double* wk, int32_t* idx, double* out2) {
   double* key = wk;            /* the M + 1 largest x, descending by pgb_psis_before */
   double* a = wk + (M + 1);    /* the tail's a_t, then its final weights w_t, ascending */
   double* bj = a + (M + 1);
   double* Lj = bj + PGB_PSIS_LANES;
   double* wj = Lj + PGB_PSIS_LANES;
-  double p1[PGB_PSIS_LANES], p2[PGB_PSIS_LANES];
+  double p1[PGB_PSIS_LANES], p2[PGB_PSIS_LANES], e1[PGB_PSIS_LANES], e2[PGB_PSIS_LANES];
   double mn = ll[0];
   for (int d = 1; d < D; ++d)
     if (ll[(int64_t)d * stride] < mn) mn = ll[(int64_t)d * stride];
@@ -211,15 +244,22 @@ PGB_HD void pgb_psis_row(const double* ll, int64_t stride, int D, int M, const p
   int T = 0;
   while (T < M && key[T] > cutoff) ++T;
   /* the draws outside the tail */
-  for (int l = 0; l < PGB_PSIS_LANES; ++l) p1[l] = p2[l] = 0.0;
+  for (int l = 0; l < PGB_PSIS_LANES; ++l) p1[l] = p2[l] = e1[l] = e2[l] = 0.0;
   for (int d = 0; d < D; ++d) {
     const double v = ll[(int64_t)d * stride];
     const double x = pgb_psis_x(v, mx);
     if (x > cutoff) continue;
-    p1[d % PGB_PSIS_LANES] = p1[d % PGB_PSIS_LANES] + pgb_psis_den_term(x, cutoff, tb);
+    const double dt = pgb_psis_den_term(x, cutoff, tb);
+    p1[d % PGB_PSIS_LANES] = p1[d % PGB_PSIS_LANES] + dt;
     p2[d % PGB_PSIS_LANES] = p2[d % PGB_PSIS_LANES] + pgb_psis_num_term(x, v, mx, tb);
+    if (kind != PGB_PSIS_G_NONE) {
+      const double gv = pgb_psis_gclamp(g[(int64_t)d * gstride]);
+      e1[d % PGB_PSIS_LANES] = e1[d % PGB_PSIS_LANES] + dt * pgb_psis_g0(gv, y, kind);
+      if (kind == PGB_PSIS_G_VALUE) e2[d % PGB_PSIS_LANES] = e2[d % PGB_PSIS_LANES] + dt * (gv * gv);
+    }
   }
   const double Dn = pgb_psis_lanes(p1), Nn = pgb_psis_lanes(p2);
+  const double Gn0 = pgb_psis_lanes(e1), Gn1 = pgb_psis_lanes(e2);
   /* the fit */
   const double ecut = pgb_exp_t(cutoff, tb->expt);
   double khat = pgb_psis_inf();
@@ -255,14 +295,37 @@ PGB_HD void pgb_psis_row(const double* ll, int64_t stride, int D, int M, const p
     if (a[t] > wmax) wmax = a[t];
     if (v > vmax) vmax = v;
   }
-  for (int l = 0; l < PGB_PSIS_LANES; ++l) p1[l] = p2[l] = 0.0;
+  for (int l = 0; l < PGB_PSIS_LANES; ++l) p1[l] = p2[l] = e1[l] = e2[l] = 0.0;
   for (int t = 0; t < T; ++t) {
     const double v = a[t] + ll[(int64_t)idx[T - 1 - t] * stride];
-    p1[t % PGB_PSIS_LANES] = p1[t % PGB_PSIS_LANES] + pgb_exp_t(a[t] - wmax, tb->expt);
+    const double et = pgb_exp_t(a[t] - wmax, tb->expt);
+    p1[t % PGB_PSIS_LANES] = p1[t % PGB_PSIS_LANES] + et;
     p2[t % PGB_PSIS_LANES] = p2[t % PGB_PSIS_LANES] + pgb_exp_t(v - vmax, tb->expt);
+    if (kind != PGB_PSIS_G_NONE) {
+      const double gv = pgb_psis_gclamp(g[(int64_t)idx[T - 1 - t] * gstride]);
+      e1[t % PGB_PSIS_LANES] = e1[t % PGB_PSIS_LANES] + et * pgb_psis_g0(gv, y, kind);
+      if (kind == PGB_PSIS_G_VALUE) e2[t % PGB_PSIS_LANES] = e2[t % PGB_PSIS_LANES] + et * (gv * gv);
+    }
   }
-  out2[0] = pgb_psis_elpd(Nn, Dn, pgb_psis_lanes(p2), pgb_psis_lanes(p1), mx, cutoff, vmax, wmax, tb);
+  const double St = pgb_psis_lanes(p1);
+  out2[0] = pgb_psis_elpd(Nn, Dn, pgb_psis_lanes(p2), St, mx, cutoff, vmax, wmax, tb);
   out2[1] = khat;
+  if (kind != PGB_PSIS_G_NONE) {
+    out2[2] = pgb_psis_ratio(Gn0, pgb_psis_lanes(e1), Dn, St, cutoff, wmax, tb);
+    if (kind == PGB_PSIS_G_VALUE) out2[3] = pgb_psis_ratio(Gn1, pgb_psis_lanes(e2), Dn, St, cutoff, wmax, tb);
+  }
+}
+
+/* PSIS-LOO of one row: out2 = (elpd_loo_i, k_i) */
+PGB_HD void pgb_psis_row(const double* ll, int64_t stride, int D, int M, const pgb_lltabs* tb, double* wk, int32_t* idx,
+                         double* out2) {
+  pgb_psis_row_any(ll, stride, (const double*)0, 0, 0.0, PGB_PSIS_G_NONE, D, M, tb, wk, idx, out2);
+}
+/* ... and its PSIS-weighted expectations of the row g: out = (elpd_loo_i, k_i, E_0[, E_1]), kind PGB_PSIS_G_VALUE
+ * (E[g], E[g^2]) or PGB_PSIS_G_PIT (the mid-p LOO-PIT of y); the first two are pgb_psis_row's bits */
+PGB_HD void pgb_psis_row_expect(const double* ll, int64_t stride, const double* g, int64_t gstride, double y, int kind, int D,
+                                int M, const pgb_lltabs* tb, double* wk, int32_t* idx, double* out) {
+  pgb_psis_row_any(ll, stride, g, gstride, y, kind, D, M, tb, wk, idx, out);
 }
 
 #endif /* PGBART_PSIS_H */

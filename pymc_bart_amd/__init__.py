@@ -16,7 +16,7 @@ from .partial import individual_conditional_expectation, partial_dependence
 from .pdp import pdp_sweep
 from .shap import shap_summary, shap_values
 from .pointwise import log_predictive_density, pointwise_log_likelihood
-from .loo import loo, psis_loo_matrix
+from .loo import loo, loo_pit, loo_predictive, psis_expectation_matrix, psis_loo_matrix
 from .summary import posterior_summary, summarize_matrix
 from .predictive import posterior_predictive, predictive_pit, predictive_summary
 
@@ -41,6 +41,6 @@ __version__ = "0.1.0"
 __all__ = [
     "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
-    "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "posterior_summary", "summarize_matrix",
+    "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix",
     "posterior_predictive", "predictive_summary", "predictive_pit", "shap_values", "shap_summary", "_abi",
 ]

@@ -279,6 +279,21 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def psis_expect_entry_point(self):
+        """``pgb_psis_expect`` (include/pgbart_pointwise.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_psis_expect
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def add_offset_entry_point(self):
+        """``pgb_add_offset`` (include/pgbart_pointwise.h): HIP library only, hence not in SYMBOLS."""
+        f = self.lib.pgb_add_offset
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     def ice_entry_point(self):
         """``pgb_predict_ice`` (include/pgbart_ice.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_predict_ice

@@ -152,11 +152,14 @@ class _Job:
         self.fidx = np.ascontiguousarray(np.asarray(table)[idx], dtype=np.int32)
         self.likelihood = likelihood
         self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None
+        self.block = None  # (run: the current block's device copies of X, y and the offset, for on_block)
 
-    def run(self, matrix: bool, summary: bool, on_block=None):
+    def run(self, matrix: bool, summary: bool, on_block=None, scratch: int = 2):
         """-> (matrix (D, n) or None, row_stats (3, n) or None, n_clamped).  ``on_block(lib, mem, md, nb, r0)``: called
         with every block's matrix still on the device (``md``: ``[D][nb]``, rows ``r0 .. r0 + nb``) in place of its
-        copy to the host -- nothing of size draws x rows then leaves the device (:mod:`pymc_bart_amd.loo`)."""
+        copy to the host -- nothing of size draws x rows then leaves the device (:mod:`pymc_bart_amd.loo`).  During
+        the call ``self.block`` holds the block's device copies ``(X, y, offset or None)``; ``scratch``: the doubles
+        per row the hook allocates on the device, counted into the block size."""
         from .sampler import default_backend
 
         be = self.backend() if self.backend is not None else default_backend()
@@ -175,7 +178,7 @@ class _Job:
             code = C.create_string_buffer(build.code, len(build.code))
             lik.code_object, lik.code_bytes = C.cast(code, C.c_void_p), len(build.code)
         per_row = 8 * (p + 2 + K + (D if matrix else 0) + (4 * (-(-D // CHUNK)) + 3 if summary else 0)
-                       + (2 if on_block is not None else 0))
+                       + (int(scratch) if on_block is not None else 0))
         block = max(64, min(n, _block_bytes() // per_row // 64 * 64))
         out = np.empty((D, n)) if matrix and on_block is None else None
         stats = np.empty((3, n)) if summary else None
@@ -200,7 +203,9 @@ class _Job:
             lib.check(rc, "pgb_pointwise_loglik")
             clamped += int(nc.value)
             if on_block is not None:
+                self.block = (xd, yd, od)
                 on_block(lib, mem, md, nb, r0)
+                self.block = None
             elif matrix:
                 out[:, r0:r1] = mem.to_host(md).reshape(D, nb)
             if summary:

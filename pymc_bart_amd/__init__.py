@@ -15,6 +15,7 @@ from .importance import compute_variable_importance, get_variable_inclusion, vi_
 from .partial import individual_conditional_expectation, partial_dependence
 from .pdp import pdp_sweep
 from .shap import shap_summary, shap_values
+from .shap_interaction import shap_interaction_summary, shap_interaction_values
 from .pointwise import log_predictive_density, pointwise_log_likelihood
 from .loo import loo, loo_pit, loo_predictive, psis_expectation_matrix, psis_loo_matrix
 from .summary import posterior_summary, summarize_matrix
@@ -42,5 +43,5 @@ __all__ = [
     "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
     "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix",
-    "posterior_predictive", "predictive_summary", "predictive_pit", "shap_values", "shap_summary", "_abi",
+    "posterior_predictive", "predictive_summary", "predictive_pit", "shap_values", "shap_summary", "shap_interaction_values", "shap_interaction_summary", "_abi",
 ]

@@ -22,6 +22,7 @@ MAX_OUTPUTS = 16  # PGB_MAX_OUTPUTS (include/pgbart_spec.h)
 MAX_NODES = 255
 PDP_LDS_MAXB = 256  # PGB_PDP_LDS_MAXB (include/pgbart_pdp.h)
 SHAP_FAST_U = 8  # PGB_SHAP_FAST_U (include/pgbart_shap.h)
+SHAPX_MAX_U = 32  # PGB_SHAPX_MAX_U (include/pgbart_shap_interaction.h)
 ABI_VERSION = 6  # PGB_ABI_VERSION of include/pgbart.h this binding was written against
 
 RULE_CONTINUOUS = 0
@@ -321,6 +322,18 @@ class PGBLibrary:
             raise NotImplementedError(f"{self.path} does not export pgb_predict_shap (HIP library only)") from None
         f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                       C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def shap_interactions_entry_point(self):
+        """``pgb_predict_shap_interactions`` (include/pgbart_shap_interaction.h): HIP library only, hence not in
+        SYMBOLS.  A library without the symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_predict_shap_interactions
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_predict_shap_interactions (HIP library only)") from None
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         f.restype = C.c_int
         return f
 

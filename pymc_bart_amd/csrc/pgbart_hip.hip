@@ -78,3 +78,4 @@
 #include "k_ppc.h"
 #include "k_pdp.h"
 #include "k_shap.h"
+#include "k_shap_interaction.h"

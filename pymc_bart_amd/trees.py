@@ -440,3 +440,15 @@ class PosteriorSampler:
         from .shap import shap_sweep
 
         return shap_sweep(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, X, picks)
+
+    def shap_interactions(self, X, picks, cols=None):
+        """Exact SHAP interaction values, ``(values (n_picks, n_outputs, n_rows, q, q), base (n_picks, n_outputs))``:
+        entry ``[s, k, i, a, b]`` is the share of the pair of columns ``cols[a]``, ``cols[b]`` in output ``k`` of the
+        draw ``picks[s]`` at row ``i``, ``[s, k, i, a, a]`` the main effect of ``cols[a]``; over all columns (``cols=None``)
+        row ``a`` sums to :meth:`shap`'s attribution (``include/pgbart_shap_interaction.h``).  ``X`` may be a handle from
+        :meth:`resident_rows`; picks may repeat, ``cols`` may not.  One ``pgb_predict_shap_interactions`` call per block
+        of rows under ``PGB_SHAP_BLOCK_BYTES``; results do not depend on the blocking.  HIP backend only."""
+        from .shap_interaction import shap_interaction_sweep
+
+        return shap_interaction_sweep(self._get_backend(), self.pool, self.forest_idx, self.m, self._n_outputs, X, picks,
+                                      cols)[:2]

@@ -145,6 +145,15 @@ class _MultiChainSampler:
         pool, table = self.pooled_history()
         return shap_sweep(first._get_backend(), pool, table, first.m, first.n_outputs, X, picks)
 
+    def shap_interactions(self, X, picks, cols=None):
+        """``PosteriorSampler.shap_interactions`` over the concatenated history: ``picks`` index the draws of all
+        chains."""
+        from .shap_interaction import shap_interaction_sweep
+
+        first = self._parts[0]
+        pool, table = self.pooled_history()
+        return shap_interaction_sweep(first._get_backend(), pool, table, first.m, first.n_outputs, X, picks, cols)[:2]
+
     def sample_posterior(self, X, draw_indices, excluded):
         want = np.asarray(draw_indices, dtype=np.int64).ravel()
         owner = np.digitize(want, self._starts[1:])  # chain of every requested draw

@@ -1064,7 +1064,7 @@ static void o_predict_rec(const pgb_tree_arrays* T, int base, int k, const doubl
  * 4 = unknown split rule on a node, 5 = the nodes reachable from node 0 do not form a tree rooted there (a node is
  * its own child or ancestor, has two parents, or the root is a child), 6 = a node deeper than PGB_MAX_DEPTH (the
  * root has depth 0; the product's walk keeps one stack entry per marginalised level), -1 = out of memory.
- * The checks and their order are the product's (pred_validate, pgb_host.h): breadth-first from node 0, left before
+ * The checks and their order are the product's (pred_validate, pgb_pred_host.h): breadth-first from node 0, left before
  * right, tree by tree after that tree's range checks.  Unreachable nodes are never walked and are left alone. */
 static int pgb_validate_forest(const pgb_tree_arrays* T, const int32_t* fidx, int32_t n_forests, int32_t m,
                                int32_t p) {

@@ -66,95 +66,56 @@ __global__ __launch_bounds__(PRED_BT) void k_ice(PredTrees T, const int32_t* __r
   }
 }
 
-// every device buffer of one call, released on every way out
-struct IceScratch {
-  uint8_t* db = nullptr;      // the packed trees (pred_pack)
-  int32_t* sel = nullptr;     // [n_cols | n_cols n_inst n_picks]: the columns, then the picks
-  ~IceScratch() {
-    if (db) (void)hipFree(db);
-    if (sel) (void)hipFree(sel);
-  }
-};
-
 extern "C" int pgb_predict_ice(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
                                const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx, const double* inst_dev,
                                int32_t n_inst, int64_t ldi, const int32_t* cols_host, int32_t n_cols,
                                const int32_t* picks_host, int32_t n_picks, double* out_dev, void* stream) {
-  if (!trees) return fail(PGB_E_INVALID, "pgb_predict_ice: trees is null");
-  if (!forest_tree_idx) return fail(PGB_E_INVALID, "pgb_predict_ice: forest_tree_idx is null");
-  if (!X_dev) return fail(PGB_E_INVALID, "pgb_predict_ice: X_dev is null");
-  if (!inst_dev) return fail(PGB_E_INVALID, "pgb_predict_ice: inst_dev is null");
-  if (!cols_host) return fail(PGB_E_INVALID, "pgb_predict_ice: cols_host is null");
-  if (!picks_host) return fail(PGB_E_INVALID, "pgb_predict_ice: picks_host is null");
-  if (!out_dev) return fail(PGB_E_INVALID, "pgb_predict_ice: out_dev is null");
-  if (n_forests < 1 || m < 1 || p < 1) return fail(PGB_E_INVALID, "pgb_predict_ice: n_forests, m and p must be >= 1");
-  if (n_inst < 1) return fail(PGB_E_INVALID, "pgb_predict_ice: n_inst must be >= 1");
-  if (n_cols < 1) return fail(PGB_E_INVALID, "pgb_predict_ice: n_cols must be >= 1");
-  if (n_picks < 1) return fail(PGB_E_INVALID, "pgb_predict_ice: n_picks must be >= 1");
-  if (n_rows < 1) return fail(PGB_E_INVALID, "pgb_predict_ice: n_rows must be >= 1");
-  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict_ice: ldx must be >= p");
-  if (ldi < p) return fail(PGB_E_INVALID, "pgb_predict_ice: ldi must be >= p");
-  const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
-  if (gx > 0x7fffffffLL) return fail(PGB_E_INVALID, "pgb_predict_ice: n_rows exceeds 2^31 - 1 tiles of 64 rows");
-  for (int c = 0; c < n_cols; ++c)
-    if (cols_host[c] < 0 || cols_host[c] >= p) {
-      snprintf(g_err, sizeof g_err, "pgb_predict_ice: cols_host[%d] = %d is outside [0, p = %d)", c, (int)cols_host[c], (int)p);
-      return PGB_E_INVALID;
-    }
+  PredCall pc("pgb_predict_ice");
+  pc.null(trees, "trees");
+  pc.null(forest_tree_idx, "forest_tree_idx");
+  pc.null(X_dev, "X_dev");
+  pc.null(inst_dev, "inst_dev");
+  pc.null(cols_host, "cols_host");
+  pc.null(picks_host, "picks_host");
+  pc.null(out_dev, "out_dev");
+  pc.forest_dims(n_forests, m, p);
+  pc.at_least_one(n_inst, "n_inst");
+  pc.at_least_one(n_cols, "n_cols");
+  pc.at_least_one(n_picks, "n_picks");
+  pc.at_least_one(n_rows, "n_rows");
+  pc.ld(ldx, p, "ldx");
+  pc.ld(ldi, p, "ldi");
+  long long gx = 0;
+  pc.tiles(n_rows, &gx);
   const size_t n_pk = (size_t)n_cols * (size_t)n_inst * (size_t)n_picks;
-  for (size_t i = 0; i < n_pk; ++i)
-    if (picks_host[i] < 0 || picks_host[i] >= n_forests) {
-      snprintf(g_err, sizeof g_err, "pgb_predict_ice: picks_host[%zu] = %d is outside [0, n_forests = %d)", i,
-               (int)picks_host[i], (int)n_forests);
-      return PGB_E_INVALID;
-    }
-  const int K = trees->n_outputs;
-  if (K < 1 || K > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
+  pc.index_vector(cols_host, (size_t)n_cols, p, "cols_host", "p");
+  pc.index_vector(picks_host, n_pk, n_forests, "picks_host", "n_forests");
+  if (pc.rc() != PGB_OK) return pc.rc();
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
   if (rc != PGB_OK) return rc;
+  const int K = trees->n_outputs;
   hipStream_t sm = (hipStream_t)stream;
-  IceScratch sc;
+  DevBuf sel;  // [n_cols | n_cols n_inst n_picks]: the columns, then the picks
   PredPack pk;
   rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, nullptr, 0, sm, &pk);  // once per call
   if (rc != PGB_OK) return rc;
-  sc.db = pk.db;
   std::vector<int32_t> hs((size_t)n_cols + n_pk);
   memcpy(hs.data(), cols_host, (size_t)n_cols * sizeof(int32_t));
   memcpy(hs.data() + n_cols, picks_host, n_pk * sizeof(int32_t));
-  HIPCHK(hipMalloc((void**)&sc.sel, hs.size() * sizeof(int32_t)));
-  HIPCHK(hipMemcpyAsync(sc.sel, hs.data(), hs.size() * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-  const int32_t* cols_dev = sc.sel;
-  const int32_t* picks_dev = sc.sel + n_cols;
+  HIPCHK(hipMalloc((void**)&sel.p, hs.size() * sizeof(int32_t)));
+  HIPCHK(hipMemcpyAsync(sel.p, hs.data(), hs.size() * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+  const int32_t* cols_dev = (const int32_t*)sel.p;
+  const int32_t* picks_dev = cols_dev + n_cols;
   // grid = (row tiles, instances, columns); the kernel strides over what y and z cannot hold
   dim3 grid((unsigned)gx, (unsigned)(n_inst < 65535 ? n_inst : 65535), (unsigned)(n_cols < 65535 ? n_cols : 65535));
   const bool ldsi = p <= PGB_ICE_LDS_MAXP;
   const size_t lds = ldsi ? (size_t)p * sizeof(double) : 0;
   const PredTrees T = pk.T;
-#define LAUNCH_ICE(L_, C_)                                                                                         \
-  do {                                                                                                             \
-    if (K == 1)                                                                                                    \
-      hipLaunchKernelGGL((k_ice<L_, C_, true>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, (int)m, K, (int)p, X_dev, \
-                         (long long)n_rows, (long long)ldx, inst_dev, (int)n_inst, (long long)ldi, cols_dev,       \
-                         (int)n_cols, picks_dev, (int)n_picks, out_dev);                                           \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_ice<L_, C_, false>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, (int)m, K, (int)p, X_dev, \
-                         (long long)n_rows, (long long)ldx, inst_dev, (int)n_inst, (long long)ldi, cols_dev,       \
-                         (int)n_cols, picks_dev, (int)n_picks, out_dev);                                           \
-  } while (0)
   WalkTimer wt(sm);
-  if (ldsi) {
-    if (pk.cont) LAUNCH_ICE(true, true);
-    else LAUNCH_ICE(true, false);
-  } else {
-    if (pk.cont) LAUNCH_ICE(false, true);
-    else LAUNCH_ICE(false, false);
-  }
-#undef LAUNCH_ICE
-  hipError_t e = hipGetLastError();
-  wt.launched();
-  hipError_t e2 = hipStreamSynchronize(sm);
-  if (e == hipSuccess && e2 == hipSuccess) wt.synced();
-  if (e != hipSuccess) return fail_hip(e, "k_ice launch");
-  if (e2 != hipSuccess) return fail_hip(e2, "k_ice");
-  return PGB_OK;
+  dispatch_bools(ldsi, pk.cont, K == 1, [&](auto L, auto C, auto K1) {
+    hipLaunchKernelGGL((k_ice<L(), C(), K1()>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, (int)m, K, (int)p, X_dev,
+                       (long long)n_rows, (long long)ldx, inst_dev, (int)n_inst, (long long)ldi, cols_dev, (int)n_cols,
+                       picks_dev, (int)n_picks, out_dev);
+  });
+  return finish_walk(hipGetLastError(), sm, wt, nullptr, "k_ice");
 }

@@ -115,18 +115,6 @@ __global__ __launch_bounds__(PDP_LT) void k_pdp_lookup(const PdpJob* __restrict_
   }
 }
 
-// every device buffer of one call, released on every way out
-struct PdpScratch {
-  uint8_t* db = nullptr;   // the packed trees (pred_pack)
-  uint8_t* job = nullptr;  // [PdpJob n_cols n_picks | the breakpoints of every profile]
-  double* tab = nullptr;   // the tables of every profile
-  ~PdpScratch() {
-    if (db) (void)hipFree(db);
-    if (job) (void)hipFree(job);
-    if (tab) (void)hipFree(tab);
-  }
-};
-
 static thread_local double g_pdp_walk_ms = -1.0, g_pdp_lookup_ms = -1.0;
 extern "C" int pgb_pdp_kernel_ms(double* walk_ms_out, double* lookup_ms_out) {
   if (!walk_ms_out || !lookup_ms_out) return fail(PGB_E_INVALID, "null argument");
@@ -162,37 +150,28 @@ extern "C" int pgb_predict_pdp(const pgb_tree_arrays* trees, const int32_t* fore
                                const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx, const int32_t* cols_host,
                                int32_t n_cols, const int32_t* picks_host, int32_t n_picks, int32_t route, double* out_dev,
                                int32_t* route_taken_host, void* stream) {
-  if (!trees) return fail(PGB_E_INVALID, "pgb_predict_pdp: trees is null");
-  if (!forest_tree_idx) return fail(PGB_E_INVALID, "pgb_predict_pdp: forest_tree_idx is null");
-  if (!X_dev) return fail(PGB_E_INVALID, "pgb_predict_pdp: X_dev is null");
-  if (!cols_host) return fail(PGB_E_INVALID, "pgb_predict_pdp: cols_host is null");
-  if (!picks_host) return fail(PGB_E_INVALID, "pgb_predict_pdp: picks_host is null");
-  if (!out_dev) return fail(PGB_E_INVALID, "pgb_predict_pdp: out_dev is null");
-  if (n_forests < 1 || m < 1 || p < 1) return fail(PGB_E_INVALID, "pgb_predict_pdp: n_forests, m and p must be >= 1");
-  if (n_cols < 1) return fail(PGB_E_INVALID, "pgb_predict_pdp: n_cols must be >= 1");
-  if (n_picks < 1) return fail(PGB_E_INVALID, "pgb_predict_pdp: n_picks must be >= 1");
-  if (n_rows < 1) return fail(PGB_E_INVALID, "pgb_predict_pdp: n_rows must be >= 1");
-  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict_pdp: ldx must be >= p");
-  if (route < PGB_PDP_ROUTE_AUTO || route > PGB_PDP_ROUTE_PROFILE)
-    return fail(PGB_E_INVALID, "pgb_predict_pdp: route must be 0 (auto), 1 (direct) or 2 (profile)");
-  const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
-  if (gx > 0x7fffffffLL) return fail(PGB_E_INVALID, "pgb_predict_pdp: n_rows exceeds 2^31 - 1 tiles of 64 rows");
-  for (int c = 0; c < n_cols; ++c)
-    if (cols_host[c] < 0 || cols_host[c] >= p) {
-      snprintf(g_err, sizeof g_err, "pgb_predict_pdp: cols_host[%d] = %d is outside [0, p = %d)", c, (int)cols_host[c], (int)p);
-      return PGB_E_INVALID;
-    }
+  PredCall pc("pgb_predict_pdp");
+  pc.null(trees, "trees");
+  pc.null(forest_tree_idx, "forest_tree_idx");
+  pc.null(X_dev, "X_dev");
+  pc.null(cols_host, "cols_host");
+  pc.null(picks_host, "picks_host");
+  pc.null(out_dev, "out_dev");
+  pc.forest_dims(n_forests, m, p);
+  pc.at_least_one(n_cols, "n_cols");
+  pc.at_least_one(n_picks, "n_picks");
+  pc.at_least_one(n_rows, "n_rows");
+  pc.ld(ldx, p, "ldx");
+  pc.require(route >= PGB_PDP_ROUTE_AUTO && route <= PGB_PDP_ROUTE_PROFILE, "route must be 0 (auto), 1 (direct) or 2 (profile)");
+  long long gx = 0;
+  pc.tiles(n_rows, &gx);
   const size_t n_job = (size_t)n_cols * (size_t)n_picks;
-  for (size_t i = 0; i < n_job; ++i)
-    if (picks_host[i] < 0 || picks_host[i] >= n_forests) {
-      snprintf(g_err, sizeof g_err, "pgb_predict_pdp: picks_host[%zu] = %d is outside [0, n_forests = %d)", i,
-               (int)picks_host[i], (int)n_forests);
-      return PGB_E_INVALID;
-    }
-  const int K = trees->n_outputs;
-  if (K < 1 || K > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
+  pc.index_vector(cols_host, (size_t)n_cols, p, "cols_host", "p");
+  pc.index_vector(picks_host, n_job, n_forests, "picks_host", "n_forests");
+  if (pc.rc() != PGB_OK) return pc.rc();
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
   if (rc != PGB_OK) return rc;
+  const int K = trees->n_outputs;
 
   // the descriptors: per column its route, per (column, pick) where its lanes come from and where its sums go
   std::vector<PdpJob> jobs(n_job);
@@ -253,50 +232,34 @@ extern "C" int pgb_predict_pdp(const pgb_tree_arrays* trees, const int32_t* fore
   }
 
   hipStream_t sm = (hipStream_t)stream;
-  PdpScratch sc;
+  DevBuf job;  // [PdpJob n_cols n_picks | the breakpoints of every profile]
+  DevBuf tab;  // the tables of every profile
   PredPack pk;
   rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, nullptr, 0, sm, &pk);  // once per call
   if (rc != PGB_OK) return rc;
-  sc.db = pk.db;
   const size_t job_bytes = n_job * sizeof(PdpJob);
   std::vector<uint8_t> hb(job_bytes + (bps.size() + 1) * sizeof(double));
   memcpy(hb.data(), jobs.data(), job_bytes);
   if (!bps.empty()) memcpy(hb.data() + job_bytes, bps.data(), bps.size() * sizeof(double));
-  HIPCHK(hipMalloc((void**)&sc.job, hb.size()));
-  HIPCHK(hipMemcpyAsync(sc.job, hb.data(), hb.size(), hipMemcpyHostToDevice, sm));
-  const PdpJob* jobs_dev = (const PdpJob*)sc.job;
-  const double* bp_dev = (const double*)(sc.job + job_bytes);
-  if (any_profile) HIPCHK(hipMalloc((void**)&sc.tab, (size_t)n_tab * sizeof(double)));
+  HIPCHK(hipMalloc((void**)&job.p, hb.size()));
+  HIPCHK(hipMemcpyAsync(job.p, hb.data(), hb.size(), hipMemcpyHostToDevice, sm));
+  const PdpJob* jobs_dev = (const PdpJob*)job.p;
+  const double* bp_dev = (const double*)(job.p + job_bytes);
+  if (any_profile) HIPCHK(hipMalloc((void**)&tab.p, (size_t)n_tab * sizeof(double)));
+  double* tab_dev = (double*)tab.p;
   const unsigned gy = (unsigned)(n_picks < 65535 ? n_picks : 65535), gz = (unsigned)(n_cols < 65535 ? n_cols : 65535);
   const PredTrees T = pk.T;
-#define LAUNCH_PDP_WALK(GRID_, PROFILE_, OUT_)                                                                       \
-  do {                                                                                                               \
-    if (pk.cont && K == 1)                                                                                           \
-      hipLaunchKernelGGL((k_pdp_walk<true, true>), GRID_, dim3(PRED_BT), 0, sm, T, pk.fidx, (int)m, K, jobs_dev,     \
-                         (int)n_picks, (int)n_cols, PROFILE_, X_dev, (long long)n_rows, (long long)ldx, bp_dev, OUT_); \
-    else if (pk.cont)                                                                                                \
-      hipLaunchKernelGGL((k_pdp_walk<true, false>), GRID_, dim3(PRED_BT), 0, sm, T, pk.fidx, (int)m, K, jobs_dev,    \
-                         (int)n_picks, (int)n_cols, PROFILE_, X_dev, (long long)n_rows, (long long)ldx, bp_dev, OUT_); \
-    else if (K == 1)                                                                                                 \
-      hipLaunchKernelGGL((k_pdp_walk<false, true>), GRID_, dim3(PRED_BT), 0, sm, T, pk.fidx, (int)m, K, jobs_dev,    \
-                         (int)n_picks, (int)n_cols, PROFILE_, X_dev, (long long)n_rows, (long long)ldx, bp_dev, OUT_); \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_pdp_walk<false, false>), GRID_, dim3(PRED_BT), 0, sm, T, pk.fidx, (int)m, K, jobs_dev,   \
-                         (int)n_picks, (int)n_cols, PROFILE_, X_dev, (long long)n_rows, (long long)ldx, bp_dev, OUT_); \
-  } while (0)
+  auto launch_walk = [&](dim3 grid, int profile, double* out) {
+    dispatch_bools(pk.cont, K == 1, [&](auto C, auto K1) {
+      hipLaunchKernelGGL((k_pdp_walk<C(), K1()>), grid, dim3(PRED_BT), 0, sm, T, pk.fidx, (int)m, K, jobs_dev, (int)n_picks,
+                         (int)n_cols, profile, X_dev, (long long)n_rows, (long long)ldx, bp_dev, out);
+    });
+    return hipGetLastError();
+  };
   hipError_t e = hipSuccess;
   WalkTimer wt_walk(sm);
-  if (any_profile) {
-    dim3 grid((unsigned)((max_slots + PRED_BT - 1) / PRED_BT), gy, gz);
-    LAUNCH_PDP_WALK(grid, 1, sc.tab);
-    e = hipGetLastError();
-  }
-  if (any_direct && e == hipSuccess) {
-    dim3 grid((unsigned)gx, gy, gz);
-    LAUNCH_PDP_WALK(grid, 0, out_dev);
-    e = hipGetLastError();
-  }
-#undef LAUNCH_PDP_WALK
+  if (any_profile) e = launch_walk(dim3((unsigned)((max_slots + PRED_BT - 1) / PRED_BT), gy, gz), 1, tab_dev);
+  if (any_direct && e == hipSuccess) e = launch_walk(dim3((unsigned)gx, gy, gz), 0, out_dev);
   wt_walk.launched();
   WalkTimer wt_look(sm);
   if (any_profile && e == hipSuccess) {
@@ -306,26 +269,12 @@ extern "C" int pgb_predict_pdp(const pgb_tree_arrays* trees, const int32_t* fore
     dim3 grid((unsigned)lx, gz);
     if (K == 1)
       hipLaunchKernelGGL((k_pdp_lookup<true>), grid, dim3(PDP_LT), lds, sm, jobs_dev, (int)n_picks, (int)n_cols, K, cap, X_dev,
-                         (long long)n_rows, (long long)ldx, bp_dev, (const double*)sc.tab, out_dev);
+                         (long long)n_rows, (long long)ldx, bp_dev, (const double*)tab_dev, out_dev);
     else
       hipLaunchKernelGGL((k_pdp_lookup<false>), grid, dim3(PDP_LT), lds, sm, jobs_dev, (int)n_picks, (int)n_cols, K, cap, X_dev,
-                         (long long)n_rows, (long long)ldx, bp_dev, (const double*)sc.tab, out_dev);
+                         (long long)n_rows, (long long)ldx, bp_dev, (const double*)tab_dev, out_dev);
     e = hipGetLastError();
   }
-  wt_look.launched();
-  hipError_t e2 = hipStreamSynchronize(sm);
-  g_pdp_walk_ms = g_pdp_lookup_ms = -1.0;
-  if (e == hipSuccess && e2 == hipSuccess) {
-    if (wt_walk.a) {
-      wt_walk.synced();
-      g_pdp_walk_ms = g_walk_ms;
-    }
-    if (wt_look.a && any_profile) {
-      wt_look.synced();
-      g_pdp_lookup_ms = g_walk_ms;
-    }
-  }
-  if (e != hipSuccess) return fail_hip(e, "k_pdp launch");
-  if (e2 != hipSuccess) return fail_hip(e2, "k_pdp");
-  return PGB_OK;
+  if (!any_profile) wt_look.drop();  // nothing was looked up: no lookup time
+  return finish_walk(e, sm, wt_look, &g_pdp_lookup_ms, "k_pdp", &wt_walk, &g_pdp_walk_ms);
 }

@@ -45,33 +45,10 @@ __device__ __forceinline__ void pw_body(const PredTrees& T, const int32_t* __res
   for (int i = lane; i < PGB_LOGT_SIZE; i += PRED_BT) pw_s_tab[PGB_LPHI_SIZE + PGB_EXPT_SIZE + i] = pgb_tab_log()[i];
   if constexpr (!LDSX) __syncthreads();
 #endif
-  if constexpr (LDSX) {
-    const long long rows_here = n_rows - row0 < PRED_BT ? n_rows - row0 : PRED_BT;
-    if (ldx == p) {
-      const double* __restrict__ src = X + row0 * ldx;
-      const int tot = (int)rows_here * p;
-      for (int i = lane; i < tot; i += PRED_BT) pw_s_x[(i % p) * 65 + i / p] = src[i];
-    } else {
-      for (int r = 0; r < (int)rows_here; ++r)
-        for (int j = lane; j < p; j += PRED_BT) pw_s_x[j * 65 + r] = X[(row0 + r) * ldx + j];
-    }
-    __syncthreads();
-  }
+  if constexpr (LDSX) pred_stage_rows(pw_s_x, X, row0, n_rows, ldx, p, lane);
   if (row >= n_rows) return;  // (lane 0 always stays: row0 < n_rows)
-  const double* __restrict__ x = X + row * ldx;
-  auto xval = [&](int j) -> double {
-    if constexpr (LDSX) return pw_s_x[j * 65 + lane];
-    else return x[j];
-  };
-  bool clean = CONT;
-  if (CONT) {
-    bool nan = false;
-    for (int j = 0; j < p; ++j) {
-      const double v = xval(j);
-      nan = nan || v != v;
-    }
-    clean = __ballot(nan) == 0ull;
-  }
+  const PredRowX<LDSX> xval{pw_s_x, X + row * ldx, lane};
+  const bool clean = pred_wave_clean<CONT>(p, xval);
   pgb_lltabs tb;
 #ifdef PGB_PW_LDS_TABLES  // (the table-placement A/B of tools/pointwise_timing.py: DESIGN.md section 7; not the product)
   tb.lphi = pw_s_tab;

@@ -166,35 +166,10 @@ __global__ __launch_bounds__(PRED_BT) void k_predict(PredTrees T, const int32_t*
   const int lane = threadIdx.x;
   const long long row0 = (long long)blockIdx.x * PRED_BT;
   const long long row = row0 + lane;
-  if constexpr (LDSX) {
-    const long long rows_here = n_rows - row0 < PRED_BT ? n_rows - row0 : PRED_BT;
-    if (ldx == p) {  // the block of rows is contiguous: fully coalesced copy
-      const double* __restrict__ src = X + row0 * ldx;
-      const int tot = (int)rows_here * p;
-      for (int i = lane; i < tot; i += PRED_BT) s_x[(i % p) * 65 + i / p] = src[i];
-    } else {
-      for (int r = 0; r < (int)rows_here; ++r)
-        for (int j = lane; j < p; j += PRED_BT) s_x[j * 65 + r] = X[(row0 + r) * ldx + j];
-    }
-    __syncthreads();
-  }
+  if constexpr (LDSX) pred_stage_rows(s_x, X, row0, n_rows, ldx, p, lane);
   if (row >= n_rows) return;
-  const double* __restrict__ x = X + row * ldx;
-  auto xval = [&](int j) -> double {
-    if constexpr (LDSX) return s_x[j * 65 + lane];
-    else return x[j];
-  };
-  // Rows without a missing value take the fixed-length walk through every tree that does not split
-  // on an excluded variable (decided per wave / per tree, so that the walk stays uniform).
-  bool clean = CONT;
-  if (CONT) {
-    bool nan = false;
-    for (int j = 0; j < p; ++j) {
-      const double v = xval(j);
-      nan = nan || v != v;
-    }
-    clean = __ballot(nan) == 0ull;
-  }
+  const PredRowX<LDSX> xval{s_x, X + row * ldx, lane};
+  const bool clean = pred_wave_clean<CONT>(p, xval);
   int stk_node[PGB_MAX_DEPTH + 2];
   double stk_w[PGB_MAX_DEPTH + 2];
   for (int d = blockIdx.y; d < n_forests; d += gridDim.y) {

@@ -20,18 +20,7 @@ __global__ __launch_bounds__(PRED_BT) void k_shap(pgb_shap_view V, const int32_t
   const int lane = threadIdx.x;
   const long long row0 = (long long)blockIdx.x * PRED_BT;
   const long long row = row0 + lane;
-  if constexpr (LDSX) {
-    const long long rows_here = n_rows - row0 < PRED_BT ? n_rows - row0 : PRED_BT;
-    if (ldx == p) {  // the block of rows is contiguous: fully coalesced copy
-      const double* __restrict__ src = X + row0 * ldx;
-      const int tot = (int)rows_here * p;
-      for (int i = lane; i < tot; i += PRED_BT) shap_s_x[(i % p) * 65 + i / p] = src[i];
-    } else {
-      for (int r = 0; r < (int)rows_here; ++r)
-        for (int j = lane; j < p; j += PRED_BT) shap_s_x[j * 65 + r] = X[(row0 + r) * ldx + j];
-    }
-    __syncthreads();
-  }
+  if constexpr (LDSX) pred_stage_rows(shap_s_x, X, row0, n_rows, ldx, p, lane);
   if (row >= n_rows) return;
   pgb_shap_view v = V;
   if (K1) v.K = 1;
@@ -46,12 +35,10 @@ __global__ __launch_bounds__(PRED_BT) void k_shap(pgb_shap_view V, const int32_t
 
 // every device buffer of one call, released on every way out
 struct ShapScratch {
-  uint8_t* db = nullptr;   // the packed trees (pred_pack: the leaf values and slopes, the forest table)
   uint8_t* rec = nullptr;  // [the header's pack | the picks]
   pgb_shap_pack pack;
   ShapScratch() { memset(&pack, 0, sizeof pack); }
   ~ShapScratch() {
-    if (db) (void)hipFree(db);
     if (rec) (void)hipFree(rec);
     pgb_shap_pack_free(&pack);
   }
@@ -67,44 +54,32 @@ extern "C" int pgb_shap_kernel_ms(double* ms_out) {
 extern "C" int pgb_predict_shap(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
                                 const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx, const int32_t* picks_host,
                                 int32_t n_picks, double* out_dev, double* base_host_out, void* stream) {
-  if (!trees) return fail(PGB_E_INVALID, "pgb_predict_shap: trees is null");
-  if (!forest_tree_idx) return fail(PGB_E_INVALID, "pgb_predict_shap: forest_tree_idx is null");
-  if (!X_dev) return fail(PGB_E_INVALID, "pgb_predict_shap: X_dev is null");
-  if (!picks_host) return fail(PGB_E_INVALID, "pgb_predict_shap: picks_host is null");
-  if (!out_dev) return fail(PGB_E_INVALID, "pgb_predict_shap: out_dev is null");
-  if (!base_host_out) return fail(PGB_E_INVALID, "pgb_predict_shap: base_host_out is null");
-  if (n_forests < 1 || m < 1 || p < 1) return fail(PGB_E_INVALID, "pgb_predict_shap: n_forests, m and p must be >= 1");
-  if (n_picks < 1) return fail(PGB_E_INVALID, "pgb_predict_shap: n_picks must be >= 1");
-  if (n_rows < 1) return fail(PGB_E_INVALID, "pgb_predict_shap: n_rows must be >= 1");
-  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict_shap: ldx must be >= p");
-  const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
-  if (gx > 0x7fffffffLL) return fail(PGB_E_INVALID, "pgb_predict_shap: n_rows exceeds 2^31 - 1 tiles of 64 rows");
-  for (int s = 0; s < n_picks; ++s)
-    if (picks_host[s] < 0 || picks_host[s] >= n_forests) {
-      snprintf(g_err, sizeof g_err, "pgb_predict_shap: picks_host[%d] = %d is outside [0, n_forests = %d)", s,
-               (int)picks_host[s], (int)n_forests);
-      return PGB_E_INVALID;
-    }
+  PredCall pc("pgb_predict_shap");
+  pc.null(trees, "trees");
+  pc.null(forest_tree_idx, "forest_tree_idx");
+  pc.null(X_dev, "X_dev");
+  pc.null(picks_host, "picks_host");
+  pc.null(out_dev, "out_dev");
+  pc.null(base_host_out, "base_host_out");
+  pc.forest_dims(n_forests, m, p);
+  pc.at_least_one(n_picks, "n_picks");
+  pc.at_least_one(n_rows, "n_rows");
+  pc.ld(ldx, p, "ldx");
+  long long gx = 0;
+  pc.tiles(n_rows, &gx);
+  pc.index_vector(picks_host, (size_t)n_picks, n_forests, "picks_host", "n_forests");
+  if (pc.rc() != PGB_OK) return pc.rc();
+  pc.n_outputs(trees);
   const int K = trees->n_outputs;
-  if (K < 1 || K > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
-  // out_dev holds n_picks K p n_rows doubles: their bytes must fit a 64-bit size (and the index arithmetic)
-  {
-    const uint64_t lim = (uint64_t)1 << 60;
-    uint64_t cells = (uint64_t)n_picks;
-    const uint64_t f[3] = {(uint64_t)K, (uint64_t)p, (uint64_t)n_rows};
-    for (int i = 0; i < 3; ++i) {
-      if (cells > lim / f[i])
-        return fail(PGB_E_INVALID, "pgb_predict_shap: out_dev of n_picks x K x p x n_rows doubles overflows a 64-bit size");
-      cells *= f[i];
-    }
-  }
+  pc.cells_fit({n_picks, K, p, n_rows}, "n_picks x K x p x n_rows");
+  if (pc.rc() != PGB_OK) return pc.rc();
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
   if (rc != PGB_OK) return rc;
 
   ShapScratch sc;
   const int prc = pgb_shap_pack_build(trees, p, &sc.pack);  // once per call
-  if (prc == -1) return fail(PGB_E_NOMEM, "pgb_predict_shap: the leaf records do not fit host memory");
-  if (prc != 0) return fail(PGB_E_INVALID, "pgb_predict_shap: the history's leaf paths number more than 2^31 - 1 splits");
+  if (prc == -1) return pc.refuse(PGB_E_NOMEM, "the leaf records do not fit host memory");
+  if (prc != 0) return pc.refuse(PGB_E_INVALID, "the history's leaf paths number more than 2^31 - 1 splits");
   const bool lin = trees->slope && trees->xbar && trees->svar;
   {
     const pgb_shap_view hv = pgb_shap_pack_view(&sc.pack, sc.pack.buf, trees->value, lin ? trees->slope : nullptr, K);
@@ -115,7 +90,6 @@ extern "C" int pgb_predict_shap(const pgb_tree_arrays* trees, const int32_t* for
   PredPack pk;
   rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, nullptr, 0, sm, &pk);
   if (rc != PGB_OK) return rc;
-  sc.db = pk.db;
   const size_t o_picks = (sc.pack.bytes + 7) & ~(size_t)7;
   std::vector<uint8_t> hb(o_picks + (size_t)n_picks * sizeof(int32_t));
   memcpy(hb.data(), sc.pack.buf, sc.pack.bytes);
@@ -127,33 +101,10 @@ extern "C" int pgb_predict_shap(const pgb_tree_arrays* trees, const int32_t* for
   dim3 grid((unsigned)gx, (unsigned)(n_picks < 65535 ? n_picks : 65535));
   const bool ldsx = p <= PRED_LDS_MAXP;
   const size_t lds = ldsx ? (size_t)p * 65 * sizeof(double) : 0;
-#define LAUNCH_SHAP(L_, C_)                                                                                          \
-  do {                                                                                                               \
-    if (K == 1)                                                                                                      \
-      hipLaunchKernelGGL((k_shap<L_, C_, true>), grid, dim3(PRED_BT), lds, sm, dv, pk.fidx, (int)m, (int)p, X_dev,   \
-                         (long long)n_rows, (long long)ldx, picks_dev, (int)n_picks, out_dev);                       \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_shap<L_, C_, false>), grid, dim3(PRED_BT), lds, sm, dv, pk.fidx, (int)m, (int)p, X_dev,  \
-                         (long long)n_rows, (long long)ldx, picks_dev, (int)n_picks, out_dev);                       \
-  } while (0)
   WalkTimer wt(sm);
-  if (ldsx) {
-    if (pk.cont) LAUNCH_SHAP(true, true);
-    else LAUNCH_SHAP(true, false);
-  } else {
-    if (pk.cont) LAUNCH_SHAP(false, true);
-    else LAUNCH_SHAP(false, false);
-  }
-#undef LAUNCH_SHAP
-  hipError_t e = hipGetLastError();
-  wt.launched();
-  hipError_t e2 = hipStreamSynchronize(sm);
-  g_shap_ms = -1.0;
-  if (e == hipSuccess && e2 == hipSuccess && wt.a) {
-    wt.synced();
-    g_shap_ms = g_walk_ms;
-  }
-  if (e != hipSuccess) return fail_hip(e, "k_shap launch");
-  if (e2 != hipSuccess) return fail_hip(e2, "k_shap");
-  return PGB_OK;
+  dispatch_bools(ldsx, pk.cont, K == 1, [&](auto L, auto C, auto K1) {
+    hipLaunchKernelGGL((k_shap<L(), C(), K1()>), grid, dim3(PRED_BT), lds, sm, dv, pk.fidx, (int)m, (int)p, X_dev,
+                       (long long)n_rows, (long long)ldx, picks_dev, (int)n_picks, out_dev);
+  });
+  return finish_walk(hipGetLastError(), sm, wt, &g_shap_ms, "k_shap");
 }

@@ -12,8 +12,6 @@
 //           header's -- whatever the grid, the row blocks and the column subset are.  A leaf of at most PGB_SHAP_FAST_U
 //           slots keeps its slots in registers (the header's loops unrolled); a longer path (up to PGB_SHAPX_MAX_U
 //           slots: the host refuses more) uses private memory.  K is a run-time value: one instance serves every K.
-#include <algorithm>
-
 #include "pgbart_shap_interaction.h"
 
 template <bool LDSX, bool CONT>
@@ -26,18 +24,7 @@ __global__ __launch_bounds__(PRED_BT) void k_shap_interaction(pgb_shap_view V, c
   const int lane = threadIdx.x;
   const long long row0 = (long long)blockIdx.x * PRED_BT;
   const long long row = row0 + lane;
-  if constexpr (LDSX) {
-    const long long rows_here = n_rows - row0 < PRED_BT ? n_rows - row0 : PRED_BT;
-    if (ldx == p) {  // the block of rows is contiguous: fully coalesced copy
-      const double* __restrict__ src = X + row0 * ldx;
-      const int tot = (int)rows_here * p;
-      for (int i = lane; i < tot; i += PRED_BT) shapx_s_x[(i % p) * 65 + i / p] = src[i];
-    } else {
-      for (int r = 0; r < (int)rows_here; ++r)
-        for (int j = lane; j < p; j += PRED_BT) shapx_s_x[j * 65 + r] = X[(row0 + r) * ldx + j];
-    }
-    __syncthreads();
-  }
+  if constexpr (LDSX) pred_stage_rows(shapx_s_x, X, row0, n_rows, ldx, p, lane);
   if (row >= n_rows) return;
   const pgb_shap_view v = V;
   const size_t per_pick = (size_t)v.K * (size_t)q * (size_t)q * (size_t)n_rows;
@@ -60,72 +47,40 @@ extern "C" int pgb_predict_shap_interactions(const pgb_tree_arrays* trees, const
                                              int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
                                              const int32_t* cols_host, int32_t n_cols, const int32_t* picks_host,
                                              int32_t n_picks, double* out_dev, double* base_host_out, void* stream) {
-#define SHAPX_ "pgb_predict_shap_interactions: "
-  if (!trees) return fail(PGB_E_INVALID, SHAPX_ "trees is null");
-  if (!forest_tree_idx) return fail(PGB_E_INVALID, SHAPX_ "forest_tree_idx is null");
-  if (!X_dev) return fail(PGB_E_INVALID, SHAPX_ "X_dev is null");
-  if (!cols_host) return fail(PGB_E_INVALID, SHAPX_ "cols_host is null");
-  if (!picks_host) return fail(PGB_E_INVALID, SHAPX_ "picks_host is null");
-  if (!out_dev) return fail(PGB_E_INVALID, SHAPX_ "out_dev is null");
-  if (!base_host_out) return fail(PGB_E_INVALID, SHAPX_ "base_host_out is null");
-  if (n_forests < 1 || m < 1 || p < 1) return fail(PGB_E_INVALID, SHAPX_ "n_forests, m and p must be >= 1");
-  if (n_cols < 1) return fail(PGB_E_INVALID, SHAPX_ "n_cols must be >= 1");
-  if (n_picks < 1) return fail(PGB_E_INVALID, SHAPX_ "n_picks must be >= 1");
-  if (n_rows < 1) return fail(PGB_E_INVALID, SHAPX_ "n_rows must be >= 1");
-  if (ldx < p) return fail(PGB_E_INVALID, SHAPX_ "ldx must be >= p");
-  const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
-  if (gx > 0x7fffffffLL) return fail(PGB_E_INVALID, SHAPX_ "n_rows exceeds 2^31 - 1 tiles of 64 rows");
-  for (int c = 0; c < n_cols; ++c)
-    if (cols_host[c] < 0 || cols_host[c] >= p) {
-      snprintf(g_err, sizeof g_err, SHAPX_ "cols_host[%d] = %d is outside [0, p = %d)", c, (int)cols_host[c], (int)p);
-      return PGB_E_INVALID;
-    }
-  {  // a column named twice (sorted pairs: p itself may be far larger than n_cols)
-    std::vector<std::pair<int32_t, int32_t>> by(n_cols);
-    for (int c = 0; c < n_cols; ++c) by[c] = {cols_host[c], c};
-    std::sort(by.begin(), by.end());
-    for (int c = 1; c < n_cols; ++c)
-      if (by[c].first == by[c - 1].first) {
-        snprintf(g_err, sizeof g_err, SHAPX_ "cols_host[%d] = %d repeats cols_host[%d]", (int)by[c].second, (int)by[c].first,
-                 (int)by[c - 1].second);
-        return PGB_E_INVALID;
-      }
-  }
-  for (int s = 0; s < n_picks; ++s)
-    if (picks_host[s] < 0 || picks_host[s] >= n_forests) {
-      snprintf(g_err, sizeof g_err, SHAPX_ "picks_host[%d] = %d is outside [0, n_forests = %d)", s, (int)picks_host[s],
-               (int)n_forests);
-      return PGB_E_INVALID;
-    }
+  PredCall pc("pgb_predict_shap_interactions");
+  pc.null(trees, "trees");
+  pc.null(forest_tree_idx, "forest_tree_idx");
+  pc.null(X_dev, "X_dev");
+  pc.null(cols_host, "cols_host");
+  pc.null(picks_host, "picks_host");
+  pc.null(out_dev, "out_dev");
+  pc.null(base_host_out, "base_host_out");
+  pc.forest_dims(n_forests, m, p);
+  pc.at_least_one(n_cols, "n_cols");
+  pc.at_least_one(n_picks, "n_picks");
+  pc.at_least_one(n_rows, "n_rows");
+  pc.ld(ldx, p, "ldx");
+  long long gx = 0;
+  pc.tiles(n_rows, &gx);
+  pc.index_vector(cols_host, (size_t)n_cols, p, "cols_host", "p");
+  pc.distinct(cols_host, n_cols);
+  pc.index_vector(picks_host, (size_t)n_picks, n_forests, "picks_host", "n_forests");
+  if (pc.rc() != PGB_OK) return pc.rc();
+  pc.n_outputs(trees);
   const int K = trees->n_outputs;
-  if (K < 1 || K > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
-  // out_dev holds n_picks K n_cols n_cols n_rows doubles: their bytes must fit a 64-bit size (and the index arithmetic)
-  {
-    const uint64_t lim = (uint64_t)1 << 60;
-    uint64_t cells = (uint64_t)n_picks;
-    const uint64_t f[4] = {(uint64_t)K, (uint64_t)n_cols, (uint64_t)n_cols, (uint64_t)n_rows};
-    for (int i = 0; i < 4; ++i) {
-      if (cells > lim / f[i])
-        return fail(PGB_E_INVALID, SHAPX_ "out_dev of n_picks x K x n_cols x n_cols x n_rows doubles overflows a 64-bit size");
-      cells *= f[i];
-    }
-  }
+  pc.cells_fit({n_picks, K, n_cols, n_cols, n_rows}, "n_picks x K x n_cols x n_cols x n_rows");
+  if (pc.rc() != PGB_OK) return pc.rc();
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
   if (rc != PGB_OK) return rc;
 
   ShapScratch sc;
   const int prc = pgb_shap_pack_build(trees, p, &sc.pack);  // once per call
-  if (prc == -1) return fail(PGB_E_NOMEM, SHAPX_ "the leaf records do not fit host memory");
-  if (prc != 0) return fail(PGB_E_INVALID, SHAPX_ "the history's leaf paths number more than 2^31 - 1 splits");
-  {
-    const int slots = pgb_shapx_pack_slots(&sc.pack);
-    if (slots > PGB_SHAPX_MAX_U) {
-      snprintf(g_err, sizeof g_err,
-               SHAPX_ "trees holds a leaf of %d slots (the columns of its path and its regressor), the limit is %d "
-                      "(PGB_SHAPX_MAX_U)", slots, (int)PGB_SHAPX_MAX_U);
-      return PGB_E_INVALID;
-    }
-  }
+  if (prc == -1) return pc.refuse(PGB_E_NOMEM, "the leaf records do not fit host memory");
+  if (prc != 0) return pc.refuse(PGB_E_INVALID, "the history's leaf paths number more than 2^31 - 1 splits");
+  const int slots = pgb_shapx_pack_slots(&sc.pack);
+  if (slots > PGB_SHAPX_MAX_U)
+    return pc.refuse(PGB_E_INVALID, "trees holds a leaf of %d slots (the columns of its path and its regressor), the limit is %d "
+                                    "(PGB_SHAPX_MAX_U)", slots, (int)PGB_SHAPX_MAX_U);
   const bool lin = trees->slope && trees->xbar && trees->svar;
   {
     const pgb_shap_view hv = pgb_shap_pack_view(&sc.pack, sc.pack.buf, trees->value, lin ? trees->slope : nullptr, K);
@@ -136,7 +91,6 @@ extern "C" int pgb_predict_shap_interactions(const pgb_tree_arrays* trees, const
   PredPack pk;
   rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, nullptr, 0, sm, &pk);
   if (rc != PGB_OK) return rc;
-  sc.db = pk.db;
   // [the header's pack | the picks | pos[p]]
   const size_t o_picks = (sc.pack.bytes + 7) & ~(size_t)7;
   const size_t o_pos = o_picks + (size_t)n_picks * sizeof(int32_t);
@@ -156,28 +110,10 @@ extern "C" int pgb_predict_shap_interactions(const pgb_tree_arrays* trees, const
   dim3 grid((unsigned)gx, (unsigned)(n_picks < 65535 ? n_picks : 65535));
   const bool ldsx = p <= PRED_LDS_MAXP;
   const size_t lds = ldsx ? (size_t)p * 65 * sizeof(double) : 0;
-#define LAUNCH_SHAPX(L_, C_)                                                                                            \
-  hipLaunchKernelGGL((k_shap_interaction<L_, C_>), grid, dim3(PRED_BT), lds, sm, dv, pk.fidx, (int)m, (int)p, X_dev,    \
-                     (long long)n_rows, (long long)ldx, pos_dev, (int)n_cols, picks_dev, (int)n_picks, out_dev)
   WalkTimer wt(sm);
-  if (ldsx) {
-    if (pk.cont) LAUNCH_SHAPX(true, true);
-    else LAUNCH_SHAPX(true, false);
-  } else {
-    if (pk.cont) LAUNCH_SHAPX(false, true);
-    else LAUNCH_SHAPX(false, false);
-  }
-#undef LAUNCH_SHAPX
-#undef SHAPX_
-  hipError_t e = hipGetLastError();
-  wt.launched();
-  hipError_t e2 = hipStreamSynchronize(sm);
-  g_shapx_ms = -1.0;
-  if (e == hipSuccess && e2 == hipSuccess && wt.a) {
-    wt.synced();
-    g_shapx_ms = g_walk_ms;
-  }
-  if (e != hipSuccess) return fail_hip(e, "k_shap_interaction launch");
-  if (e2 != hipSuccess) return fail_hip(e2, "k_shap_interaction");
-  return PGB_OK;
+  dispatch_bools(ldsx, pk.cont, [&](auto L, auto C) {
+    hipLaunchKernelGGL((k_shap_interaction<L(), C()>), grid, dim3(PRED_BT), lds, sm, dv, pk.fidx, (int)m, (int)p, X_dev,
+                       (long long)n_rows, (long long)ldx, pos_dev, (int)n_cols, picks_dev, (int)n_picks, out_dev);
+  });
+  return finish_walk(hipGetLastError(), sm, wt, &g_shapx_ms, "k_shap_interaction");
 }

@@ -1456,244 +1456,3 @@ extern "C" int pgb_get_split_weights(pgb_handle* h, double* out) {
   for (int j = 0; j < h->d.p; ++j) out[j] = (double)a[j] * (h->d.max_prior * pgb_pow2(-PGB_ALPHA_BITS));
   return PGB_OK;
 }
-
-// The history of a prediction (pgb_predict, pgb_pointwise_loglik, pgb_predict_ice), checked: a malformed one
-// (truncated file, mismatched m, hand-built arrays) is an error, not an out-of-bounds walk and not a walk that never
-// ends.  Beyond the ranges of the indices, every tree must be WALKABLE ("Walkable histories"):
-//   * the nodes reachable from node 0 form a tree rooted there: no node is its own child or ancestor, none has two
-//     parents, and the root is nobody's child -- the general walk of pgb_pred_walk.h follows left / right until it
-//     meets a leaf, so a cycle would keep a wave on the device for ever;
-//   * no node lies deeper than PGB_MAX_DEPTH (the root has depth 0) -- a walk that marginalises pushes one entry per
-//     level on a private stack of PGB_MAX_DEPTH + 2 entries.  Both samplers stop splitting at that depth
-//     (prior_leaf), so only loaded or hand-built arrays can break the rule.
-// Nodes that cannot be reached from the root are never walked and are left alone.  The oracle's pgb_validate_forest
-// makes the same checks in the same order and pgb_predict reports them with the same messages.
-#define PGB_MSG_NOT_A_TREE "a tree's nodes do not form a tree rooted at node 0 (a node is its own ancestor or has two parents)"
-#define PGB_MSG_TOO_DEEP "a tree is deeper than PGB_MAX_DEPTH = " PGB_STR(PGB_MAX_DEPTH)
-static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m,
-                         int32_t p) {
-  if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
-  // a malformed history (truncated file, mismatched m) is an error, not an out-of-bounds walk
-  if (trees->n_trees < 0 || trees->total_nodes < 0) return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
-  for (long long i = 0; i < (long long)n_forests * m; ++i)
-    if (forest_tree_idx[i] < 0 || forest_tree_idx[i] >= trees->n_trees)
-      return fail(PGB_E_INVALID, "forest_tree_idx entry outside [0, n_trees)");
-  std::vector<int32_t> dep, todo;  // depth of every node reached from the root (-1: not reached), the nodes to visit
-  for (int t = 0; t < trees->n_trees; ++t) {
-    const int base = trees->node_off[t], end = trees->node_off[t + 1];
-    if (base < 0 || end <= base || end > trees->total_nodes)
-      return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
-    for (int g = base; g < end; ++g) {
-      if (trees->var[g] < 0) continue;
-      if (trees->var[g] >= p) return fail(PGB_E_INVALID, "a tree splits on a column X does not have");
-      if (trees->rule && trees->rule[g] != PGB_RULE_CONTINUOUS && trees->rule[g] != PGB_RULE_ONEHOT &&
-          trees->rule[g] != PGB_RULE_SUBSET)
-        return fail(PGB_E_INVALID, "a split node carries an unknown split rule");
-      if (trees->left[g] < 0 || trees->right[g] < 0 || trees->left[g] >= end - base || trees->right[g] >= end - base)
-        return fail(PGB_E_INVALID, "tree arrays are inconsistent (node_off / left / right)");
-    }
-    // walkable: breadth-first from node 0, left before right; a child met twice (or the root met at all) is a
-    // second parent or a cycle
-    const int nn = end - base;
-    dep.assign((size_t)nn, -1);
-    todo.clear();
-    dep[0] = 0;
-    todo.push_back(0);
-    for (size_t q = 0; q < todo.size(); ++q) {
-      const int k = todo[q];
-      if (trees->var[base + k] < 0) continue;
-      const int32_t ch[2] = {trees->left[base + k], trees->right[base + k]};
-      for (int s = 0; s < 2; ++s) {
-        if (dep[ch[s]] >= 0) return fail(PGB_E_INVALID, PGB_MSG_NOT_A_TREE);
-        dep[ch[s]] = dep[k] + 1;
-        if (dep[ch[s]] > PGB_MAX_DEPTH) return fail(PGB_E_INVALID, PGB_MSG_TOO_DEEP);
-        todo.push_back(ch[s]);
-      }
-    }
-  }
-  return PGB_OK;
-}
-
-// ... and packed into ONE upload (freed by the caller: pk->db) for the walk of pgb_pred_walk.h
-struct PredPack {
-  uint8_t* db = nullptr;
-  PredTrees T;
-  const int32_t* fidx = nullptr;  // [n_forests][m], device
-  bool cont = true;               // every split of every tree is `x <= v`: the instances without the rule dispatch
-};
-static int pred_pack(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests, int32_t m, int32_t p,
-                     const int32_t* excluded_host, int32_t n_excluded, hipStream_t sm, PredPack* pk) {
-  const int K = trees->n_outputs, N = trees->total_nodes, NT = trees->n_trees;
-  std::vector<uint8_t> excl((size_t)p, 0);
-  for (int e = 0; e < n_excluded; ++e)
-    if (excluded_host[e] >= 0 && excluded_host[e] < p) excl[excluded_host[e]] = 1;
-  const bool lin = trees->slope && trees->xbar && trees->svar;
-  // one upload buffer: [PNode N | FNode N | value N K | (slope N K | xbar N) | root NT | fidx | (svar N)]
-  const size_t o_fn = (size_t)N * sizeof(PNode);
-  const size_t o_val = o_fn + (size_t)N * sizeof(FNode);
-  const size_t o_slope = o_val + (size_t)N * K * 8;
-  const size_t o_xbar = o_slope + (lin ? (size_t)N * K * 8 : 0);
-  const size_t o_root = o_xbar + (lin ? (size_t)N * 8 : 0);
-  const size_t o_f = o_root + (size_t)NT * sizeof(int2);
-  const size_t o_svar = o_f + (size_t)n_forests * m * 4;
-  const size_t bytes = o_svar + (lin ? (size_t)N * 4 : 0);
-  std::vector<uint8_t> hb(bytes);
-  PNode* hn = (PNode*)hb.data();
-  FNode* hf = (FNode*)(hb.data() + o_fn);
-  int2* hroot = (int2*)(hb.data() + o_root);
-  std::vector<int> depth_of;
-  bool cont = true;  // every split of every tree is `x <= v`: the instance without the rule dispatch
-  int32_t* hsvar = (int32_t*)(hb.data() + o_svar);
-  for (int t = 0; t < NT; ++t) {
-    const int base = trees->node_off[t], end = trees->node_off[t + 1];
-    // depth of the tree and whether it can take the fixed-length walk (<= 255 nodes, children after
-    // their parent as both backends build them, no split on an excluded variable)
-    const int nn = end - base;
-    bool general = nn > 255 || nn < 1;
-    int depth = 0;
-    depth_of.assign((size_t)(nn > 0 ? nn : 1), 0);
-    for (int k = 0; k < nn && !general; ++k) {
-      const int g = base + k;
-      if (trees->var[g] < 0) continue;
-      const int l = trees->left[g], r = trees->right[g];
-      if (l <= k || r <= k || l >= nn || r >= nn) { general = true; break; }
-      if (trees->var[g] < p && excl[trees->var[g]]) general = true;
-      depth_of[l] = depth_of[r] = depth_of[k] + 1;
-      if (depth_of[k] + 1 > depth) depth = depth_of[k] + 1;
-    }
-    if (depth > 255) general = true;
-    hroot[t] = make_int2(base, general ? 0x100 : depth);
-    for (int g = base; g < end; ++g) {
-      PNode z;
-      z.var = trees->var[g];
-      if (z.var >= p) return fail(PGB_E_INVALID, "a tree splits on a column X does not have");
-      z.left = z.var >= 0 ? base + trees->left[g] : -1;
-      z.right = z.var >= 0 ? base + trees->right[g] : -1;
-      const int rule = z.var >= 0 && trees->rule ? trees->rule[g] : PGB_RULE_CONTINUOUS;  // the node's own
-      if (rule != PGB_RULE_CONTINUOUS) cont = false;
-      z.flags = z.var >= 0 ? ((rule << 1) | (excl[z.var] ? 1 : 0)) : 0;
-      z.split = trees->split[g];
-      z.cnt = (double)trees->count[g];
-      hn[g] = z;
-      FNode f;
-      f.pad = 0;
-      if (z.var >= 0 && !general) {
-        f.split = z.split; f.var = z.var; f.left = (uint8_t)trees->left[g]; f.right = (uint8_t)trees->right[g];
-      } else {  // a leaf points at itself: x <= +inf for every value that is not NaN
-        f.split = __builtin_inf(); f.var = 0; f.left = f.right = (uint8_t)((g - base) & 255);
-      }
-      hf[g] = f;
-      if (lin) {
-        const int js = trees->svar[g];
-        hsvar[g] = (js >= 0 && js < p && !excl[js]) ? js : -1;
-      }
-    }
-  }
-  memcpy(hb.data() + o_val, trees->value, (size_t)N * K * 8);
-  if (lin) {
-    memcpy(hb.data() + o_slope, trees->slope, (size_t)N * K * 8);
-    memcpy(hb.data() + o_xbar, trees->xbar, (size_t)N * 8);
-  }
-  memcpy(hb.data() + o_f, forest_tree_idx, (size_t)n_forests * m * 4);
-  uint8_t* db = nullptr;
-  HIPCHK(hipMalloc((void**)&db, bytes));
-  hipError_t e = hipMemcpyAsync(db, hb.data(), bytes, hipMemcpyHostToDevice, sm);
-  if (e != hipSuccess) { (void)hipFree(db); return fail_hip(e, "hipMemcpyAsync"); }
-  PredTrees& T = pk->T;
-  T.node = (const PNode*)db;
-  T.value = (const double*)(db + o_val);
-  T.slope = lin ? (const double*)(db + o_slope) : nullptr;
-  T.xbar = lin ? (const double*)(db + o_xbar) : nullptr;
-  T.fnode = (const FNode*)(db + o_fn);
-  T.root = (const int2*)(db + o_root);
-  T.svar = lin ? (const int32_t*)(db + o_svar) : nullptr;
-  pk->db = db;
-  pk->fidx = (const int32_t*)(db + o_f);
-  pk->cont = cont;
-  return PGB_OK;
-}
-
-// PGB_WALK_TIMING=1 (environment, read per call): the walk kernel of pgb_predict / pgb_predict_ice alone, between two
-// HIP events on the call's stream; pgb_walk_kernel_ms (include/pgbart_ice.h) reports the last one of the calling
-// thread (tools/ice_timing.py).  Unset: no event is created.
-static thread_local double g_walk_ms = -1.0;
-struct WalkTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  hipStream_t sm;
-  explicit WalkTimer(hipStream_t s) : sm(s) {
-    const char* ev = getenv("PGB_WALK_TIMING");
-    if (!ev || atoi(ev) <= 0) return;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess || hipEventRecord(a, sm) != hipSuccess) {
-      (void)hipGetLastError();
-      drop();
-    }
-  }
-  void launched() {
-    if (a && hipEventRecord(b, sm) != hipSuccess) drop();
-  }
-  void synced() {  // (after the stream has been synchronised)
-    float ms = 0.f;
-    if (a && hipEventElapsedTime(&ms, a, b) == hipSuccess) g_walk_ms = (double)ms;
-  }
-  void drop() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    a = b = nullptr;
-  }
-  ~WalkTimer() { drop(); }
-};
-extern "C" int pgb_walk_kernel_ms(double* ms_out) {
-  if (!ms_out) return fail(PGB_E_INVALID, "null argument");
-  *ms_out = g_walk_ms;
-  return PGB_OK;
-}
-
-extern "C" int pgb_predict(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests,
-                           int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
-                           const int32_t* excluded_host, int32_t n_excluded,
-                           double* out_dev, void* stream) {
-  if (!trees || !forest_tree_idx || !X_dev || !out_dev) return fail(PGB_E_INVALID, "null argument");
-  if (ldx < p) return fail(PGB_E_INVALID, "pgb_predict: ldx must be >= p");  // (rows that overlap: never a layout)
-  if (trees->n_outputs < 1 || trees->n_outputs > PGB_MAX_OUTPUTS) return fail(PGB_E_INVALID, "n_outputs");
-  if (n_forests < 1 || n_rows < 1) return PGB_OK;
-  int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
-  if (rc != PGB_OK) return rc;
-  hipStream_t sm = (hipStream_t)stream;
-  PredPack pk;
-  rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, excluded_host, n_excluded, sm, &pk);
-  if (rc != PGB_OK) return rc;
-  const int K = trees->n_outputs;
-  const PredTrees T = pk.T;
-  uint8_t* db = pk.db;
-  const bool cont = pk.cont;
-  // one wave per workgroup; enough workgroups to fill the chip, each looping over its share of forests
-  const long long gx = (n_rows + PRED_BT - 1) / PRED_BT;
-  long long want_wgs = p <= PRED_LDS_MAXP ? 16384 : 4096;  // measured at cfg2 (32 forests x 100k rows): 10.0 vs 11.7 ms
-  if (const char* ev = getenv("PGB_PRED_WGS")) want_wgs = atoll(ev) > 0 ? atoll(ev) : want_wgs;
-  long long gy = (want_wgs + gx - 1) / gx;
-  if (gy > n_forests) gy = n_forests;
-  if (gy < 1) gy = 1;
-  dim3 grid((unsigned)gx, (unsigned)gy);
-#define LAUNCH_PRED(L_, C_, LDS_)                                                                               \
-  hipLaunchKernelGGL((k_predict<L_, C_>), grid, dim3(PRED_BT), (LDS_), sm, T, pk.fidx, n_forests, \
-                     m, K, (int)p, X_dev, (long long)n_rows, (long long)ldx, out_dev)
-  const size_t lds = (size_t)p * 65 * sizeof(double);
-  WalkTimer wt(sm);
-  if (p <= PRED_LDS_MAXP) {
-    if (cont) LAUNCH_PRED(true, true, lds);
-    else LAUNCH_PRED(true, false, lds);
-  } else {
-    if (cont) LAUNCH_PRED(false, true, 0);
-    else LAUNCH_PRED(false, false, 0);
-  }
-#undef LAUNCH_PRED
-  hipError_t e = hipGetLastError();
-  wt.launched();
-  hipError_t e2 = hipStreamSynchronize(sm);
-  if (e == hipSuccess && e2 == hipSuccess) wt.synced();
-  (void)hipFree(db);
-  if (e != hipSuccess) return fail_hip(e, "k_predict launch");
-  if (e2 != hipSuccess) return fail_hip(e2, "k_predict");
-  return PGB_OK;
-}
-

@@ -1,16 +1,14 @@
 // pgb_pointwise_host.h -- part of pgbart_hip.hip (not a standalone header): host side of pgb_pointwise_loglik
 // (include/pgbart_pointwise.h).  Handle-free like pgb_predict, whose history validation and node packing it shares
-// (pred_validate, pred_pack: pgb_host.h).  Everything is checked before the walk kernel is launched.
+// (pred_validate, pred_pack: pgb_pred_host.h).  Everything is checked before the walk kernel is launched.
 
-// every device buffer of one call, released on every way out
+// every device buffer of one call next to the packed trees, released on every way out
 struct PwScratch {
-  uint8_t* db = nullptr;        // the packed trees (pred_pack)
   double* params = nullptr;     // [n_forests][PGB_PW_PSTRIDE]
   double* partial = nullptr;    // [n_chunks][4][n_rows]
   unsigned long long* words = nullptr;  // [0] clamp count, [1] non-finite y / aux, [2] offset beyond the limit
   hipModule_t mod = nullptr;
   ~PwScratch() {
-    if (db) (void)hipFree(db);
     if (params) (void)hipFree(params);
     if (partial) (void)hipFree(partial);
     if (words) (void)hipFree(words);
@@ -145,7 +143,6 @@ extern "C" int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t*
   PredPack pk;
   rc = pred_pack(trees, forest_tree_idx, n_forests, m, p, nullptr, 0, sm, &pk);
   if (rc != PGB_OK) return rc;
-  sc.db = pk.db;
   HIPCHK(hipMalloc((void**)&sc.params, hp.size() * sizeof(double)));
   HIPCHK(hipMemcpyAsync(sc.params, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice, sm));
   const int n_chunks = (n_forests + PGB_PW_CHUNK - 1) / PGB_PW_CHUNK;
@@ -179,23 +176,10 @@ extern "C" int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t*
                     (void*)&nr, (void*)&ld, (void*)&A, (void*)&mode};
     HIPCHK(hipModuleLaunchKernel(fn, grid.x, grid.y, 1, PRED_BT, 1, 1, (unsigned)lds, sm, args, nullptr));
   } else {
-#define LAUNCH_PW(L_, C_)                                                                                          \
-  do {                                                                                                             \
-    if (K == 1)                                                                                                    \
-      hipLaunchKernelGGL((k_pointwise<L_, C_, true>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, n_forests, m, K,  \
-                         (int)p, X_dev, (long long)n_rows, (long long)ldx, A);                                     \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_pointwise<L_, C_, false>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, n_forests, m, K, \
-                         (int)p, X_dev, (long long)n_rows, (long long)ldx, A);                                     \
-  } while (0)
-    if (ldsx) {
-      if (pk.cont) LAUNCH_PW(true, true);
-      else LAUNCH_PW(true, false);
-    } else {
-      if (pk.cont) LAUNCH_PW(false, true);
-      else LAUNCH_PW(false, false);
-    }
-#undef LAUNCH_PW
+    dispatch_bools(ldsx, pk.cont, K == 1, [&](auto L, auto C, auto K1) {
+      hipLaunchKernelGGL((k_pointwise<L(), C(), K1()>), grid, dim3(PRED_BT), lds, sm, T, pk.fidx, n_forests, m, K, (int)p,
+                         X_dev, (long long)n_rows, (long long)ldx, A);
+    });
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "k_pointwise launch");

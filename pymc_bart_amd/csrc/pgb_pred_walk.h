@@ -51,6 +51,46 @@ struct PredTrees {
 #define PRED_LDS_MAXP 126
 #endif
 
+// LDSX: the wave's tile of rows row0 .. row0 + 63 (those below n_rows) into s_x[p][65], and the barrier after it.
+__device__ __forceinline__ void pred_stage_rows(double* s_x, const double* X, long long row0, long long n_rows, long long ldx,
+                                                int p, int lane) {
+  const long long rows_here = n_rows - row0 < PRED_BT ? n_rows - row0 : PRED_BT;
+  if (ldx == p) {  // the block of rows is contiguous: fully coalesced copy
+    const double* __restrict__ src = X + row0 * ldx;
+    const int tot = (int)rows_here * p;
+    for (int i = lane; i < tot; i += PRED_BT) s_x[(i % p) * 65 + i / p] = src[i];
+  } else {
+    for (int r = 0; r < (int)rows_here; ++r)
+      for (int j = lane; j < p; j += PRED_BT) s_x[j * 65 + r] = X[(row0 + r) * ldx + j];
+  }
+  __syncthreads();
+}
+
+// xval of a lane that walks its own row: column j from the staged tile (LDSX) or from the row itself
+template <bool LDSX>
+struct PredRowX {
+  const double* s_x;              // pred_stage_rows' tile
+  const double* __restrict__ x;   // X + row * ldx
+  int lane;
+  __device__ __forceinline__ double operator()(int j) const {
+    if constexpr (LDSX) return s_x[j * 65 + lane];
+    else return x[j];
+  }
+};
+
+// Rows without a missing value take the fixed-length walk through every tree that does not split on an excluded
+// variable (decided per wave / per tree, so that the walk stays uniform): pred_walk_forest's `clean`.
+template <bool CONT, class XV>
+__device__ __forceinline__ bool pred_wave_clean(int p, XV xval) {
+  if (!CONT) return false;
+  bool nan = false;
+  for (int j = 0; j < p; ++j) {
+    const double v = xval(j);
+    nan = nan || v != v;
+  }
+  return __ballot(nan) == 0ull;
+}
+
 // acc[0 .. K-1] = the sum over the m trees `forest_of_draw` names of the leaf values the row reaches; xval(j) is the
 // row's value of column j.  `clean`: wave-uniform, no lane of the wave holds a missing value (CONT only).  The order of
 // the additions is the contract: tree 0 first, within a tree that marginalises depth-first, left first.

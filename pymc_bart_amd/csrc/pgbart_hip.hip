@@ -69,6 +69,7 @@
 #include "k_pointwise.h"
 #include "k_export.h"
 #include "pgb_host.h"
+#include "pgb_pred_host.h"
 #include "pgb_checkpoint.h"
 #include "pgb_probe.h"
 #include "pgb_pointwise_host.h"

@@ -58,16 +58,13 @@ def _summarised(g, grid, cols, picks, spec, keep_pd: bool):
     column])``.  Every block of the sweep stays on the device: a column's ``[samples][K * rows]`` part of it is the
     matrix ``pgb_row_summary`` takes; only with ``keep_pd`` is the block also copied to the host."""
     from .pdp import _checked, device_blocks
-    from .pointwise import _chains
+    from .shap import _history
     from .summary import _hip, _result, _spec, _summary_block
-    from .trees import pooled_history
 
-    parts = _chains(g)
+    parts, (pool, table) = _history(g)
     be = _hip(parts[0]._get_backend())
     lib, mem = be.lib, be.mem
     K, m = int(parts[0].n_outputs), int(parts[0].m)
-    cached = getattr(g, "pooled_history", None)
-    pool, table = cached() if cached is not None else pooled_history(parts)
     D = int(picks.shape[1])
     q, hdi_k, code = _spec(D, *spec)
     X, cols, picks = _checked(grid, False, cols, picks, int(np.asarray(table).shape[0]), 0)

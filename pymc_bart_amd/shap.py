@@ -46,10 +46,11 @@ def _checked(X, resident: bool, picks, n_draws: int):
     return X, np.ascontiguousarray(picks, dtype=np.int32)
 
 
-def blocks(n_picks: int, K: int, p: int, n: int):
-    """The row blocks ``(r0, r1)`` of one sweep: multiples of 64 rows whose attributions stay under
-    ``PGB_SHAP_BLOCK_BYTES`` (at least 64 rows)."""
-    rows = max(64, _block_bytes() // (8 * n_picks * K * p) // 64 * 64)
+def blocks(cells_per_row: int, n: int):
+    """The row blocks ``(r0, r1)`` of one sweep of ``n`` rows: multiples of 64 rows whose ``cells_per_row`` doubles
+    each (attributions: ``n_picks K p``; interactions: ``n_picks K q q``) stay under ``PGB_SHAP_BLOCK_BYTES`` (at
+    least 64 rows)."""
+    rows = max(64, _block_bytes() // (8 * cells_per_row) // 64 * 64)
     return [(r0, min(n, r0 + rows)) for r0 in range(0, n, rows)]
 
 
@@ -70,7 +71,7 @@ def device_blocks(be, pool, table, m: int, K: int, X, picks):
     xd = X if mem.is_resident(X) else mem.from_host(X)
     carr = pool.as_c()
     base = np.empty((n_picks, K))
-    for r0, r1 in blocks(n_picks, K, p, n):
+    for r0, r1 in blocks(n_picks * K * p, n):
         od = mem.empty((n_picks * K * p * (r1 - r0),), np.float64)
         rc = call(C.byref(carr), fidx.ctypes.data, int(fidx.shape[0]), int(m), mem.ptr(xd) + 8 * r0 * p, r1 - r0, p, p,
                   picks.ctypes.data, n_picks, mem.ptr(od), base.ctypes.data, mem.stream_ptr)
@@ -139,6 +140,23 @@ def shap_values(sampler, X, draws=None, samples=None, random_seed=None) -> dict:
     return {"values": values, "base": base, "draws": np.asarray(picks, dtype=np.int64).copy()}
 
 
+def _summary_result(by, Q: int, hdi_k, base, K: int, strength_key: str, extra: dict) -> dict:
+    """The dict a summary returns, from ``by`` -- the rows of ``pgb_row_summary`` (mean, variance, ``Q`` quantiles,
+    HDI) over ``(K, n_rows, ...)`` -- and the draws' ``base``: ``strength_key`` names the mean over the rows of
+    ``|mean|``, the ``K`` axis is dropped when the sampler has one output, ``extra`` is added as it is."""
+    res = {"mean": by[0].copy(), "sd": np.sqrt(by[1]), "var": by[1].copy(), "quantiles": by[2:2 + Q].copy(),
+           "hdi": by[2 + Q:4 + Q].copy() if hdi_k else None, strength_key: np.abs(by[0]).mean(axis=1),
+           "base_mean": base.mean(axis=0)}
+    if K == 1:
+        for key in ("mean", "sd", "var", strength_key, "base_mean"):
+            res[key] = res[key][0]
+        res["quantiles"] = res["quantiles"][:, 0]
+        if res["hdi"] is not None:
+            res["hdi"] = res["hdi"][:, 0]
+    res.update(extra)
+    return res
+
+
 def shap_summary(sampler, X, draws=None, samples=None, random_seed=None, quantiles=(0.03, 0.5, 0.97),
                  hdi_prob=0.94) -> dict:
     """Posterior summaries of the attributions of :func:`shap_values`, computed where they lie: per block of rows one
@@ -171,15 +189,6 @@ def shap_summary(sampler, X, draws=None, samples=None, random_seed=None, quantil
         stats[:, :, :, r0:r1] = _summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, p, r1 - r0)
         base = b.copy()
     by = np.ascontiguousarray(np.swapaxes(stats, 2, 3))  # (rows of the summary, K, n, p)
-    res = {"mean": by[0].copy(), "sd": np.sqrt(by[1]), "var": by[1].copy(), "quantiles": by[2:2 + Q].copy(),
-           "hdi": by[2 + Q:4 + Q].copy() if hdi_k else None, "importance": np.abs(by[0]).mean(axis=1),
-           "base_mean": base.mean(axis=0)}
-    if K == 1:
-        for key in ("mean", "sd", "var", "importance", "base_mean"):
-            res[key] = res[key][0]
-        res["quantiles"] = res["quantiles"][:, 0]
-        if res["hdi"] is not None:
-            res["hdi"] = res["hdi"][:, 0]
-    res.update({"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
-                "draws": np.asarray(picks, dtype=np.int64).copy()})
-    return res
+    return _summary_result(by, Q, hdi_k, base, K, "importance",
+                           {"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
+                            "draws": np.asarray(picks, dtype=np.int64).copy()})

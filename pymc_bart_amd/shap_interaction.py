@@ -19,7 +19,7 @@ import ctypes as C
 
 import numpy as np
 
-from .shap import _block_bytes, _checked, _history, _picks
+from .shap import _checked, _history, _picks, _summary_result, blocks
 
 
 def _checked_cols(cols, p: int) -> np.ndarray:
@@ -41,13 +41,6 @@ def _checked_cols(cols, p: int) -> np.ndarray:
     return np.ascontiguousarray(idx, dtype=np.int32)
 
 
-def blocks(n_picks: int, K: int, q: int, n: int):
-    """The row blocks ``(r0, r1)`` of one sweep: multiples of 64 rows whose ``q x q`` matrices stay under
-    ``PGB_SHAP_BLOCK_BYTES`` (at least 64 rows)."""
-    rows = max(64, _block_bytes() // (8 * n_picks * K * q * q) // 64 * 64)
-    return [(r0, min(n, r0 + rows)) for r0 in range(0, n, rows)]
-
-
 def _entry(lib):
     """``pgb_predict_shap_interactions`` of the backend's library; ``NotImplementedError`` naming it when the library
     has none."""
@@ -66,7 +59,7 @@ def device_blocks(be, pool, table, m: int, K: int, X, cols, picks):
     xd = X if mem.is_resident(X) else mem.from_host(X)
     carr = pool.as_c()
     base = np.empty((n_picks, K))
-    for r0, r1 in blocks(n_picks, K, q, n):
+    for r0, r1 in blocks(n_picks * K * q * q, n):
         od = mem.empty((n_picks * K * q * q * (r1 - r0),), np.float64)
         rc = call(C.byref(carr), fidx.ctypes.data, int(fidx.shape[0]), int(m), mem.ptr(xd) + 8 * r0 * p, r1 - r0, p, p,
                   cols.ctypes.data, q, picks.ctypes.data, n_picks, mem.ptr(od), base.ctypes.data, mem.stream_ptr)
@@ -146,15 +139,6 @@ def shap_interaction_summary(sampler, X, cols=None, draws=None, samples=None, ra
         stats[..., r0:r1] = _summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, nq, nq, r1 - r0)
         base = b.copy()
     by = np.ascontiguousarray(np.moveaxis(stats, 4, 2))  # (rows of the summary, K, n, q, q)
-    res = {"mean": by[0].copy(), "sd": np.sqrt(by[1]), "var": by[1].copy(), "quantiles": by[2:2 + Q].copy(),
-           "hdi": by[2 + Q:4 + Q].copy() if hdi_k else None, "strength": np.abs(by[0]).mean(axis=1),
-           "base_mean": base.mean(axis=0)}
-    if K == 1:
-        for key in ("mean", "sd", "var", "strength", "base_mean"):
-            res[key] = res[key][0]
-        res["quantiles"] = res["quantiles"][:, 0]
-        if res["hdi"] is not None:
-            res["hdi"] = res["hdi"][:, 0]
-    res.update({"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
-                "draws": np.asarray(picks, dtype=np.int64).copy(), "cols": cols.astype(np.int64)})
-    return res
+    return _summary_result(by, Q, hdi_k, base, K, "strength",
+                           {"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
+                            "draws": np.asarray(picks, dtype=np.int64).copy(), "cols": cols.astype(np.int64)})

@@ -184,7 +184,7 @@ def deep_forest(kind, variant):
 
 @pytest.mark.parametrize("kind,variant", DEEP, ids=_ids(DEEP))
 def test_oracle_validator_and_shap_packer_accept_the_depth_64_forest(oracle, kind, variant):
-    """pgb_host.h says the prediction validators never refuse a sampler's own tree; here the sampler's deepest."""
+    """pgb_pred_host.h says the prediction validators never refuse a sampler's own tree; here the sampler's deepest."""
     import _shap_host as H
 
     c, forest = deep_forest(kind, variant)

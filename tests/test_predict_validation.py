@@ -1,5 +1,5 @@
 """Histories that cannot be walked are refused before anything touches a device (``pred_validate`` in
-``pgb_host.h``, ``pgb_validate_forest`` in the oracle): a tree whose nodes do not form a tree rooted at node 0 would
+``pgb_pred_host.h``, ``pgb_validate_forest`` in the oracle): a tree whose nodes do not form a tree rooted at node 0 would
 keep the general walk of ``pgb_pred_walk.h`` going for ever, one deeper than ``PGB_MAX_DEPTH`` would overrun its stack.
 
 Every check precedes the first HIP call, so the library answers without a GPU; host buffers stand in for device memory

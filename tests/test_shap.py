@@ -268,11 +268,11 @@ def test_refusals_of_the_python_layer(hand, oracle):
 
 def test_blocks_are_multiples_of_64_under_the_limit(monkeypatch):
     monkeypatch.setenv("PGB_SHAP_BLOCK_BYTES", "65536")
-    assert shap_mod.blocks(2, 1, 4, 300) == [(0, 300)]                     # 64 rows x 64 B = 4 KiB: 1024 rows fit
-    assert shap_mod.blocks(4, 3, 5, 300) == [(0, 128), (128, 256), (256, 300)]
-    assert shap_mod.blocks(64, 16, 100, 130) == [(0, 64), (64, 128), (128, 130)]   # never fewer than 64 rows
+    assert shap_mod.blocks(2 * 1 * 4, 300) == [(0, 300)]                     # 64 rows x 64 B = 4 KiB: 1024 rows fit
+    assert shap_mod.blocks(4 * 3 * 5, 300) == [(0, 128), (128, 256), (256, 300)]
+    assert shap_mod.blocks(64 * 16 * 100, 130) == [(0, 64), (64, 128), (128, 130)]   # never fewer than 64 rows
     monkeypatch.delenv("PGB_SHAP_BLOCK_BYTES")
-    assert shap_mod.blocks(50, 1, 50, 100000) == [(0, 53632), (53632, 100000)]      # 1 GiB: 20 000 B per row
+    assert shap_mod.blocks(50 * 1 * 50, 100000) == [(0, 53632), (53632, 100000)]      # 1 GiB: 20 000 B per row
 
 
 @pytest.mark.parametrize("so", ["libpgbart_hip.so", "libpgbart_hip_p128.so"])

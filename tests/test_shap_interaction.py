@@ -307,11 +307,11 @@ def test_refusals_of_the_python_layer(hand, oracle):
 
 def test_blocks_account_for_the_square_of_the_columns(monkeypatch):
     monkeypatch.setenv("PGB_SHAP_BLOCK_BYTES", "65536")
-    assert mod.blocks(2, 1, 2, 300) == [(0, 300)]                          # 64 B per row: 1024 rows fit
-    assert mod.blocks(4, 1, 4, 300) == [(0, 128), (128, 256), (256, 300)]  # 512 B per row
-    assert mod.blocks(4, 3, 5, 130) == [(0, 64), (64, 128), (128, 130)]    # 2400 B per row: never fewer than 64 rows
+    assert mod.blocks(2 * 1 * 2 * 2, 300) == [(0, 300)]                          # 64 B per row: 1024 rows fit
+    assert mod.blocks(4 * 1 * 4 * 4, 300) == [(0, 128), (128, 256), (256, 300)]  # 512 B per row
+    assert mod.blocks(4 * 3 * 5 * 5, 130) == [(0, 64), (64, 128), (128, 130)]    # 2400 B per row: never fewer than 64 rows
     monkeypatch.delenv("PGB_SHAP_BLOCK_BYTES")
-    assert mod.blocks(50, 1, 10, 100000) == [(0, 26816), (26816, 53632), (53632, 80448), (80448, 100000)]  # 1 GiB: 40 000 B per row
+    assert mod.blocks(50 * 1 * 10 * 10, 100000) == [(0, 26816), (26816, 53632), (53632, 80448), (80448, 100000)]  # 1 GiB: 40 000 B per row
 
 
 @pytest.mark.parametrize("so", ["libpgbart_hip.so", "libpgbart_hip_p128.so"])

@@ -88,9 +88,43 @@ class TorchHipMemory:
         t = self.torch.from_numpy(np.ascontiguousarray(arr))
         return t.to(self.device, non_blocking=False)
 
+    def device_rows(self, obj):
+        """What a stored-draw consumer reads when ``X`` is ``obj``: ``None`` -- the host path -- for anything that is
+        not a torch tensor and for a tensor on the CPU; otherwise a float64 tensor ``(n, p)`` on this GPU that is dense
+        and row-major, so that ``data_ptr()`` with ``ldx = p`` (and ``+ 8 r0 p`` for a block of rows) is the matrix.
+        A row-major contiguous matrix is handed back as it is (no copy, same ``data_ptr()``); a 1-D tensor becomes its
+        ``(n, 1)`` view; a tensor that requires grad is detached; any other view (a column slice, a row step, a
+        transpose) is copied once on the device by ``.contiguous()``, on the current stream.  ``ValueError`` for a
+        tensor on another device, for another dtype (no silent cast) and for a shape that is no matrix.  Looks at the
+        tensor's type, device, dtype, shape, strides and ``requires_grad`` only: no GPU is touched."""
+        import torch
+
+        if not isinstance(obj, torch.Tensor):
+            return None
+        if obj.device != self.device:
+            if obj.device.type == "cpu":
+                return None
+            raise ValueError(f"X is a tensor on {obj.device}, but this sampler's backend runs on {self.device}: "
+                             f"move it there (or pass a host matrix)")
+        if obj.dtype != torch.float64:
+            raise ValueError(f"X is a device tensor of dtype {obj.dtype}; the kernels read float64 and nothing is cast "
+                             f"silently: pass X.double()")
+        if obj.dim() == 1:
+            obj = obj[:, None]
+        if obj.dim() != 2 or int(obj.shape[0]) < 1 or int(obj.shape[1]) < 1:
+            raise ValueError(f"X must be a matrix (n_rows, p), got shape {tuple(obj.shape)}")
+        if obj.requires_grad:
+            obj = obj.detach()
+        return obj if obj.is_contiguous() else obj.contiguous()
+
     def is_resident(self, obj) -> bool:
-        """True for a float64 matrix that already lives in this GPU's HBM (a tensor from :meth:`from_host`)."""
-        return isinstance(obj, self.torch.Tensor) and obj.is_cuda and obj.dtype == self.torch.float64
+        """True for what :meth:`device_rows` hands back as it is: a dense row-major float64 matrix in this GPU's HBM
+        (a tensor from :meth:`from_host`).  False -- never an exception -- for everything else, including the tensors
+        :meth:`device_rows` refuses or has to reshape, detach or copy."""
+        try:
+            return obj is not None and self.device_rows(obj) is obj
+        except ValueError:
+            return False
 
     def empty(self, shape, dtype=np.float64):
         tdt = {np.float64: self.torch.float64, np.int32: self.torch.int32}[np.dtype(dtype).type]
@@ -111,3 +145,11 @@ class TorchHipMemory:
 
     def synchronize(self) -> None:
         self.torch.cuda.synchronize(self.device)
+
+
+def device_rows(mem, X):
+    """``(X, resident)`` at the top of a stored-draw consumer: the dense device matrix ``mem.device_rows`` makes of a
+    device tensor and ``True``, or ``X`` itself and ``False`` (the host path; always, on a backend whose memory has no
+    device tensors)."""
+    rows = getattr(mem, "device_rows", lambda a: None)(X)
+    return (X, False) if rows is None else (rows, True)

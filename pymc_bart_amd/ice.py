@@ -17,6 +17,8 @@ import os
 
 import numpy as np
 
+from ._device import device_rows
+
 
 def _block_bytes() -> int:
     """Device bytes the output of one block of columns may take: ``PGB_ICE_BLOCK_BYTES``, default 1 GiB, floor 64 KiB."""
@@ -78,7 +80,7 @@ def ice_mean(be, pool, table, m: int, K: int, predict, X, instances, cols, picks
     ``cols[c]`` replaced by ``X[i, cols[c]]``.  ``be``: the backend; ``predict``: the sampler's ``sample_posterior``,
     used by a backend without ``pgb_predict_ice``."""
     mem, lib = be.mem, be.lib
-    resident = bool(getattr(mem, "is_resident", lambda a: False)(X))
+    X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
     n_draws = int(np.asarray(table).shape[0])
     X, inst, cols, picks = _checked(X, resident, instances, cols, picks, n_draws)
     n, p = (int(v) for v in X.shape)

@@ -18,6 +18,8 @@ import os
 
 import numpy as np
 
+from ._device import device_rows
+
 ROUTES = (0, 1, 2)  # PGB_PDP_ROUTE_AUTO, _DIRECT, _PROFILE
 
 
@@ -103,7 +105,7 @@ def pdp_sweep(be, pool, table, m: int, K: int, predict, X, cols, picks, route: i
     choose per column, 1 walks every row, 2 takes the profile route for every eligible column -- the result is the
     same.  ``taken``: a list that receives, per block, ``(c0, c1, r0, r1, [route of each column: 1 direct, 2 profile])``."""
     mem, lib = be.mem, be.lib
-    resident = bool(getattr(mem, "is_resident", lambda a: False)(X))
+    X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
     n_draws = int(np.asarray(table).shape[0])
     X, cols, picks = _checked(X, resident, cols, picks, n_draws, route)
     if not hasattr(lib.lib, "pgb_predict_pdp"):

@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 
+from ._device import device_rows
+
 
 def _block_bytes() -> int:
     """Device bytes the attributions of one block of rows may take: ``PGB_SHAP_BLOCK_BYTES``, default 1 GiB, floor
@@ -81,10 +83,10 @@ def device_blocks(be, pool, table, m: int, K: int, X, picks):
 
 def shap_sweep(be, pool, table, m: int, K: int, X, picks):
     """``(values (n_picks, K, n_rows, p), base (n_picks, K))`` of the draws ``picks`` (rows of ``table``; they may
-    repeat) at the rows of ``X`` (a matrix, or a handle from ``resident_rows``).  One ``pgb_predict_shap`` call per
-    block of rows; the result does not depend on the blocking."""
+    repeat) at the rows of ``X`` (a host matrix, or a device matrix: ``PosteriorSampler.resident_rows``).  One
+    ``pgb_predict_shap`` call per block of rows; the result does not depend on the blocking."""
     mem, lib = be.mem, be.lib
-    resident = bool(getattr(mem, "is_resident", lambda a: False)(X))
+    X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
     X, picks = _checked(X, resident, picks, int(np.asarray(table).shape[0]))
     _entry(lib)
     n, p = (int(v) for v in X.shape)

@@ -19,6 +19,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._device import device_rows
 from .shap import _checked, _history, _picks, _summary_result, blocks
 
 
@@ -69,10 +70,11 @@ def device_blocks(be, pool, table, m: int, K: int, X, cols, picks):
 
 def shap_interaction_sweep(be, pool, table, m: int, K: int, X, picks, cols=None):
     """``(values (n_picks, K, n_rows, q, q), base (n_picks, K), the columns (q,))`` of the draws ``picks`` (rows of ``table``; they may
-    repeat) at the rows of ``X`` (a matrix, or a handle from ``resident_rows``) between the columns ``cols`` (``None``:
-    all).  One ``pgb_predict_shap_interactions`` call per block of rows; the result does not depend on the blocking."""
+    repeat) at the rows of ``X`` (a host matrix, or a device matrix: ``PosteriorSampler.resident_rows``) between the
+    columns ``cols`` (``None``: all).  One ``pgb_predict_shap_interactions`` call per block of rows; the result does not
+    depend on the blocking."""
     mem, lib = be.mem, be.lib
-    resident = bool(getattr(mem, "is_resident", lambda a: False)(X))
+    X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
     X, picks = _checked(X, resident, picks, int(np.asarray(table).shape[0]))
     n, p = (int(v) for v in X.shape)
     cols = _checked_cols(cols, p)

@@ -15,6 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi
+from ._device import device_rows
 
 
 @dataclass
@@ -372,8 +373,13 @@ class PosteriorSampler:
         return self._backend
 
     def resident_rows(self, X):
-        """Upload ``X`` once; the returned handle is accepted by :meth:`sample_posterior` in place of the
-        matrix (backends without device memory hand the matrix back)."""
+        """Upload ``X`` once; the returned handle is accepted by :meth:`sample_posterior`, :meth:`ice_mean`,
+        :meth:`pdp_sweep`, :meth:`shap` and :meth:`shap_interactions` in place of the matrix (backends without device
+        memory hand the matrix back).  On the HIP backend the handle is a float64 torch tensor, and those five accept
+        any such "device matrix": a float64 tensor ``(n, p)`` or ``(n,)`` on the backend's GPU.  A dense row-major one
+        is read where it lies, without a copy; any other view (a column slice, a row step, a transpose) is copied once
+        on the device, on the current stream.  Another dtype, another device or another rank is a ``ValueError``
+        (``TorchHipMemory.device_rows``)."""
         be = self._get_backend()
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         if X.ndim == 1:
@@ -382,9 +388,10 @@ class PosteriorSampler:
 
     def sample_posterior(self, X, draw_indices, excluded=None) -> np.ndarray:
         be = self._get_backend()
-        # `X` may already be resident in HBM (``resident_rows``): sweeps that predict on the same rows
-        # again and again -- variable importance, partial dependence -- then upload them once
-        resident = getattr(be.mem, "is_resident", lambda a: False)(X)
+        # `X` may already be resident in HBM (``resident_rows``, or any float64 tensor on the backend's GPU): sweeps
+        # that predict on the same rows again and again -- variable importance, partial dependence -- then upload
+        # them once.  A dense row-major tensor is read where it lies, any other view through one device copy.
+        X, resident = device_rows(be.mem, X)
         if not resident:
             X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
             if X.ndim == 1:
@@ -408,8 +415,8 @@ class PosteriorSampler:
     def ice_mean(self, X, instances, cols, picks) -> np.ndarray:
         """Individual conditional expectation curves, ``(n_cols, n_inst, n_outputs, n_rows)``: entry ``[c, r, k, i]``
         is the mean over the draws ``picks[c, r, :]`` of output ``k`` predicted at ``instances[r]`` with its column
-        ``cols[c]`` replaced by ``X[i, cols[c]]`` -- summed in pick order, divided once.  ``X`` may be a handle from
-        :meth:`resident_rows`; ``instances`` is ``(n_inst, p)``, ``picks`` ``(n_cols, n_inst, n_picks)`` draw indices
+        ``cols[c]`` replaced by ``X[i, cols[c]]`` -- summed in pick order, divided once.  ``X`` may be a device
+        matrix (:meth:`resident_rows`); ``instances`` is ``(n_inst, p)``, ``picks`` ``(n_cols, n_inst, n_picks)`` draw indices
         (they may repeat).  On the HIP backend this is one fused ``pgb_predict_ice`` call per block of columns (the
         device output stays under ``PGB_ICE_BLOCK_BYTES``, default 1 GiB; results do not depend on the blocking)."""
         from .ice import ice_mean
@@ -420,7 +427,7 @@ class PosteriorSampler:
     def pdp_sweep(self, X, cols, picks, route: int = 0, taken=None) -> np.ndarray:
         """Partial dependence sweeps, ``(n_cols, n_picks, n_outputs, n_rows)``: entry ``[c, s, k, i]`` is output ``k``
         of the draw ``picks[c, s]`` predicted at ``X[i, cols[c]]`` with every other column excluded -- the bits of
-        ``sample_posterior(X, picks[c], all but cols[c])``.  ``X`` may be a handle from :meth:`resident_rows`; picks
+        ``sample_posterior(X, picks[c], all but cols[c])``.  ``X`` may be a device matrix (:meth:`resident_rows`); picks
         may repeat.  On the HIP backend this is one fused ``pgb_predict_pdp`` call per block (the device output stays
         under ``PGB_PDP_BLOCK_BYTES``, default 1 GiB: whole columns first, rows of one column when it does not fit;
         results depend neither on the blocking nor on ``route``, see ``pdp.pdp_sweep``)."""
@@ -434,7 +441,7 @@ class PosteriorSampler:
         ``[s, k, i, j]`` is the share of column ``j`` in output ``k`` of the draw ``picks[s]`` at row ``i``, the value of
         a coalition being ``sample_posterior`` with every column outside it excluded; ``base`` is the prediction with
         every column excluded, and ``base + values.sum(-1)`` the plain prediction (``include/pgbart_shap.h``).  ``X`` may
-        be a handle from :meth:`resident_rows`; picks may repeat.  One ``pgb_predict_shap`` call per block of rows (the
+        be a device matrix (:meth:`resident_rows`); picks may repeat.  One ``pgb_predict_shap`` call per block of rows (the
         device output stays under ``PGB_SHAP_BLOCK_BYTES``, default 1 GiB; results do not depend on the blocking).  HIP
         backend only."""
         from .shap import shap_sweep
@@ -445,8 +452,8 @@ class PosteriorSampler:
         """Exact SHAP interaction values, ``(values (n_picks, n_outputs, n_rows, q, q), base (n_picks, n_outputs))``:
         entry ``[s, k, i, a, b]`` is the share of the pair of columns ``cols[a]``, ``cols[b]`` in output ``k`` of the
         draw ``picks[s]`` at row ``i``, ``[s, k, i, a, a]`` the main effect of ``cols[a]``; over all columns (``cols=None``)
-        row ``a`` sums to :meth:`shap`'s attribution (``include/pgbart_shap_interaction.h``).  ``X`` may be a handle from
-        :meth:`resident_rows`; picks may repeat, ``cols`` may not.  One ``pgb_predict_shap_interactions`` call per block
+        row ``a`` sums to :meth:`shap`'s attribution (``include/pgbart_shap_interaction.h``).  ``X`` may be a device matrix
+        (:meth:`resident_rows`); picks may repeat, ``cols`` may not.  One ``pgb_predict_shap_interactions`` call per block
         of rows under ``PGB_SHAP_BLOCK_BYTES``; results do not depend on the blocking.  HIP backend only."""
         from .shap_interaction import shap_interaction_sweep
 

@@ -88,18 +88,16 @@ extern "C" int pgb_checkpoint_save(pgb_handle* h, void* host_buf, int64_t bytes)
   REFUSE_POISONED(h);  // (the state of an abandoned step is not a chain)
   Dev& d = h->d;
   const long long n = d.n, n_pad = d.n_pad;
-  const int K = d.K, KX = d.K - 1, m = d.m, p = d.p;
-  const bool lin = d.response != PGB_RESPONSE_CONSTANT;
+  const int K = d.K, m = d.m, p = d.p;
   HIPCHK(hipStreamSynchronize(h->stream));  // step calls return idle; this also covers set_* uploads and queued idle slots
   Ctrl c;
   double sd[PGB_MAX_OUTPUTS] = {0};
   int rc = read_idle_ctrl(h, &c, sd);
   if (rc != PGB_OK) return rc;
   if (c.phase != PH_IDLE) return fail(PGB_E_STATE, "device not idle");
-  std::vector<DTree> T((size_t)m);
-  HIPCHK(hipMemcpy(T.data(), d.trees, sizeof(DTree) * (size_t)m, hipMemcpyDeviceToHost));
-  long long N = 0;
-  for (int t = 0; t < m; ++t) N += T[t].n_nodes;
+  HostTrees ht;
+  if ((rc = ht.fetch(h, 0, m)) != PGB_OK) return rc;
+  const int N = ht.total_nodes();
   const int64_t need = pgb_image_bytes(n, p, m, K, (int32_t)N);
   if (bytes < need) return fail(PGB_E_INVALID, "checkpoint buffer too small");
   pgb_image_header hd;
@@ -125,43 +123,8 @@ extern "C" int pgb_checkpoint_save(pgb_handle* h, void* host_buf, int64_t bytes)
   HIPCHK(hipMemcpy(v.alpha, d.alpha + (size_t)c.alpha_cur * p, (size_t)p * sizeof(long long), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(v.cdf, d.cdfS + (size_t)c.cdf_cur * p, (size_t)p * sizeof(long long), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy2D(v.lid, (size_t)n, d.tree_lid, (size_t)n_pad, (size_t)n, (size_t)m, hipMemcpyDeviceToHost));
-  std::vector<double> hx, hsx;
-  std::vector<LinP> hl;
-  if (KX > 0) {
-    hx.resize((size_t)m * MAXN * KX);
-    HIPCHK(hipMemcpy(hx.data(), d.tvx, hx.size() * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (lin) {
-    hl.resize((size_t)m * MAXN);
-    HIPCHK(hipMemcpy(hl.data(), d.tlin, hl.size() * sizeof(LinP), hipMemcpyDeviceToHost));
-    if (KX > 0) {
-      hsx.resize((size_t)m * MAXN * KX);
-      HIPCHK(hipMemcpy(hsx.data(), d.tsx, hsx.size() * sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
-  int32_t g = 0;
-  for (int t = 0; t < m; ++t) {
-    v.node_off[t] = g;
-    for (int k = 0; k < T[t].n_nodes; ++k, ++g) {
-      const DNode& z = T[t].nd[k];
-      const bool leaf = z.var < 0;
-      const bool islin = leaf && lin && hl[(size_t)t * MAXN + k].svar >= 0;
-      v.var[g] = z.var;
-      v.left[g] = leaf ? -1 : (int32_t)z.left;
-      v.right[g] = leaf ? -1 : (int32_t)z.right;
-      v.depth[g] = z.depth;
-      v.label[g] = z.label;
-      v.svar[g] = islin ? (int32_t)hl[(size_t)t * MAXN + k].svar : -1;
-      v.count[g] = z.cnt;
-      v.split[g] = leaf ? 0.0 : z.split;
-      v.xbar[g] = islin ? hl[(size_t)t * MAXN + k].xbar : 0.0;
-      for (int o = 0; o < K; ++o) {
-        v.value[(size_t)g * K + o] = !leaf ? 0.0 : o ? hx[((size_t)t * MAXN + k) * KX + o - 1] : z.value;
-        v.slope[(size_t)g * K + o] = !islin ? 0.0 : o ? hsx[((size_t)t * MAXN + k) * KX + o - 1] : hl[(size_t)t * MAXN + k].slope;
-      }
-    }
-  }
-  v.node_off[m] = g;
+  if ((rc = ht.fetch_leaves(h, true)) != PGB_OK) return rc;
+  write_nodes(ht, node_sink(v));
   return PGB_OK;
 }
 

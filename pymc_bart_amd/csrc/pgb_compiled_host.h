@@ -5,20 +5,10 @@
 #define PGB_HEADERS_HASH 0ull  // (a build without the hash -- __graft_entry__.build passes it -- refuses every code object)
 #endif
 
-// The resident grid of the loaded kernel, as pgb_create sizes it for the built-in instances.
+// The resident grid of the loaded kernel, as pgb_create sizes it for the built-in instances (size_ll_grid).
 static void compiled_size_grid(pgb_handle* h) {
-  if (getenv("PGB_LL_GRID")) return;
-  int per_cu = 0, cus = 0;
-  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->cl_fn, BT, 0) == hipSuccess &&
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0) {
-    // (as the built-in K = 2, 3, 4 with constant leaves; the linear pass is the run-time-K path: what stays resident)
-    if (h->d.K >= 2 && h->d.K <= 4 && h->d.response == PGB_RESPONSE_CONSTANT && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;
-    long long g = (long long)per_cu * cus;
-    if (g < 256) g = 256;
-    if (g > 2048) g = 2048;
-    h->ll_grid = (int)g;
-    if (!getenv("PGB_LL_TARGET")) h->d.ll_target = h->ll_grid > 1024 ? h->ll_grid : 1024;
-  }
+  int per_cu = 0;
+  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->cl_fn, BT, 0) == hipSuccess) size_ll_grid(h, per_cu);
 }
 
 extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64_t bytes, int32_t n_params) {

@@ -17,6 +17,31 @@ static int fail_hip(hipError_t e, const char* what) {
     if (e_ != hipSuccess) return fail_hip(e_, #expr);    \
   } while (0)
 
+// one device buffer of a call, released on every way out
+struct DevBuf {
+  uint8_t* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// The kernels of a slot besides the likelihood pass, chosen once per data set (select_slot_kernels): the instance of
+// k_ctrl with its workgroup count and the instance of the row pass (k_rows<...> and k_rows_mk<...> take the same
+// arguments).  ctrl == nullptr: not chosen yet -- the first enqueue_slots after pgb_create, or after a pgb_set_data
+// that changed use_keys or has_subset, fills it in.
+typedef void (*ctrl_kernel_t)(const Dev*, int, int, Ctrl*, const InitAcc*, const Job*, const Acc*, const DPart*, const uint16_t*);
+typedef void (*rows_kernel_t)(const Dev*, int, const Cmd*, const Job*);
+typedef void (*ll_kernel_t)(const Dev*, int, int, const Cmd*, const Ctrl*, const Job*, const Acc*, const InitAcc*);
+struct SlotKernels {
+  ctrl_kernel_t ctrl = nullptr;
+  int ctrl_wgs = 0;  // P - 1, or P: + the workgroup that builds the label tables ahead
+  rows_kernel_t rows = nullptr;
+  int rows_cap = 0;  // workgroups the row pass keeps resident (enqueue_slots; K-vector instances only, else rows_grid)
+};
+
 struct pgb_handle {
   pgb_settings s;
   Dev d;
@@ -34,19 +59,18 @@ struct pgb_handle {
   int st_cur, alpha_cur;  // mirrors of Ctrl::st_cur / alpha_cur at the last idle point
   int have_data, have_y;
   int has_subset;  // any SubsetSplit column: selects the row-pass instance
-  int rows_grid;   // workgroups of the persistent row-pass grid (dispatch costs ~3.5 ns each)
+  int rows_grid = 1024;  // workgroups of the persistent row-pass grid (dispatch costs ~3.5 ns each)
   int ll_grid;     // ... of the log-likelihood pass
-  int rows_mk_cap; // K-vector row pass: workgroups its instance keeps resident (0: not queried yet)
   // 16-bit order keys: decided by pgb_set_data alone, for the data it was last given.  This one flag picks the KEYS
   // instance of k_ctrl and the F32 instance of the row pass TOGETHER (they disagree on the stride of the chunk-count
   // rows otherwise); d.XK16 is xk16_buf while it is set and null while it is not
   int use_keys;
   uint16_t* xk16_buf;  // [p][n_pad], allocated by the first pgb_set_data that wants keys, kept until pgb_destroy
-  // the instance of k_loglik this sampler launches (family / outputs / response)
-  void (*ll_kernel)(const Dev*, int, int, const Cmd*, const Ctrl*, const Job*, const Acc*, const InitAcc*);
-  int sigma_dirty;
-  double inv_sigma2;
-  double lik_param2;
+  SlotKernels slot_k;
+  ll_kernel_t ll_kernel;  // the instance of k_loglik this sampler launches (family / outputs / response)
+  int sigma_dirty = 1;
+  double inv_sigma2 = 1.0;
+  double lik_param2 = 1.0;
   int lower_host;      // mirror of the batch cursor
   int last_lower, last_n;
   double slots_per_step;  // running estimate of the working slots one astep needs ...
@@ -77,7 +101,7 @@ struct pgb_handle {
   hipModule_t cl_module;
   hipFunction_t cl_fn;
   hipFunction_t cl_probe;
-  int cl_nparams;
+  int cl_nparams = -1;
   pgb_compiled_params cl_prm;
   double* cl_aux;
   std::vector<double> y_host, off_host;
@@ -159,6 +183,46 @@ static int dalloc(pgb_handle* h, T** p, size_t count) {
   return rc;
 }
 
+// One buffer of the sampler: allocated (in call order: the slab's layout), stored in its member of the handle or of
+// Dev -- const-qualified ones included -- and given its initial contents on the sampler's stream, all from ONE count.
+enum FillKind { FILL_NONE, FILL_ZERO, FILL_BYTE, FILL_F64, FILL_LINP };
+template <typename T>
+static int dbuf(pgb_handle* h, T** dst, size_t count, FillKind kind = FILL_NONE, double v = 0.0) {
+  typedef typename std::remove_const<T>::type U;
+  U* q = nullptr;
+  const int rc = dalloc(h, &q, count);
+  if (rc != PGB_OK) return rc;
+  *dst = q;
+  const dim3 grid((unsigned)((count + 255) / 256));
+  hipError_t e = hipSuccess;
+  if (kind == FILL_ZERO || kind == FILL_BYTE) e = hipMemsetAsync(q, kind == FILL_BYTE ? (int)v : 0, count * sizeof(U), h->stream);
+  if constexpr (std::is_same<U, double>::value)
+    if (kind == FILL_F64) hipLaunchKernelGGL(k_fill_f64, grid, dim3(256), 0, h->stream, q, (long long)count, v);
+  if constexpr (std::is_same<U, LinP>::value)
+    if (kind == FILL_LINP) hipLaunchKernelGGL(k_init_linp, grid, dim3(256), 0, h->stream, q, (long long)count);
+  return e == hipSuccess ? PGB_OK : fail_hip(e, "hipMemsetAsync");
+}
+
+// The likelihood pass is a persistent grid too, and its instances differ a lot in registers (probit 88
+// VGPRs, K = 4 softmax 154): the grid is what the chosen instance can keep resident -- 5 workgroups per
+// CU for probit, 3 for K = 4 -- so that no workgroup waits for another to finish; the pass aims for at
+// least as many work items.  (cfg4: 1024 -> 1280 workgroups, k_loglik 40.3 -> 37.5 us.)
+// per_cu: what the occupancy query answered for the instance -- a built-in one (pgb_create) or the loaded module
+// kernel (pgb_set_loglik_code; its linear pass is the run-time-K path: what stays resident).
+static void size_ll_grid(pgb_handle* h, int per_cu) {
+  int cus = 0;
+  if (getenv("PGB_LL_GRID") || per_cu <= 0) return;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus <= 0) return;
+  // (K = 2, 3, 4 with constant leaves: the instances are compiled for PGB_LLK_WGS workgroups per CU and measured best
+  //  there -- cfg5: 768 workgroups 27.2-27.9 us, 1024 28.1-31.2 us, 1280 30.5-31.0 us -- whatever else would fit)
+  if (h->d.K >= 2 && h->d.K <= 4 && h->d.response == PGB_RESPONSE_CONSTANT && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;
+  long long g = (long long)per_cu * cus;
+  if (g < 256) g = 256;
+  if (g > 2048) g = 2048;
+  h->ll_grid = (int)g;
+  if (!getenv("PGB_LL_TARGET")) h->d.ll_target = h->ll_grid > 1024 ? h->ll_grid : 1024;
+}
+
 extern "C" const char* pgb_last_error(void) { return g_err; }
 extern "C" const char* pgb_backend_name(void) { return "hip-gfx950"; }
 extern "C" int32_t pgb_max_particles(void) { return PGB_MAX_PARTICLES; }
@@ -166,7 +230,6 @@ extern "C" int32_t pgb_abi_version(void) { return PGB_ABI_VERSION; }
 
 // The instance of k_loglik a sampler launches, chosen once: per number of outputs (loops unrolled for
 // K = 2, 3, 4), per family for single-output constant leaves (one family's code per instance).
-typedef void (*ll_kernel_t)(const Dev*, int, int, const Cmd*, const Ctrl*, const Job*, const Acc*, const InitAcc*);
 static ll_kernel_t select_ll_kernel(int K, bool lin, int family) {
   if (family == PGB_FAMILY_COMPILED) return nullptr;  // (a module kernel for any K: pgb_set_loglik_code)
   if (K > 1 && lin) return k_loglik<0, -1, true>;
@@ -235,62 +298,15 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
              hipGetErrorString(e0), ndev);
     return PGB_E_DEVICE;
   }
-  pgb_handle* h = new pgb_handle();
+  pgb_handle* h = new pgb_handle();  // (value-initialised: zero but for the defaults the struct states)
   g_live_handles.fetch_add(1);
   h->s = *s;
   h->stream = (hipStream_t)stream;
-  h->stream_out = nullptr;
-  h->slab = nullptr;
-  h->slab_used = 0;
-  h->slot = 0;
-  h->has_subset = 0;
-  h->rows_grid = 1024;
-  h->rows_mk_cap = 0;
-  h->use_keys = 0;
-  h->xk16_buf = nullptr;
-  h->prof_buf = nullptr;
-  h->prof = 0;
-  for (int k = 0; k < PK_COUNT; ++k) {
-    h->ev_used[k] = 0;
-    h->prof_ms[k] = 0.0;
-    h->prof_launches[k] = 0;
-    h->prof_wgs[k] = 0;
-  }
-  h->cb_fn = nullptr;
-  h->cb_ctx = nullptr;
-  h->cl_module = nullptr;
-  h->cl_fn = nullptr;
-  h->cl_probe = nullptr;
-  h->cl_nparams = -1;
-  memset(&h->cl_prm, 0, sizeof h->cl_prm);
-  h->cl_aux = nullptr;
-  h->out_host = h->out_dev = nullptr;
-  h->st_dense = nullptr;
-  h->out_valid = 0;
-  h->poisoned = 0;
-  h->job_running = 0;
-  h->job_rc = PGB_OK;
-  h->device = 0;
   (void)hipGetDevice(&h->device);
-  h->prof_clock_ms = 0.0;
-  h->prof_clock_launches = 0;
-  h->prof_slot0 = 0;
   if (const char* e = getenv("PGB_ROWS_GRID")) h->rows_grid = atoi(e) > 0 ? atoi(e) : h->rows_grid;
   h->ll_grid = h->rows_grid;
   if (const char* e = getenv("PGB_LL_GRID")) h->ll_grid = atoi(e) > 0 ? atoi(e) : h->ll_grid;
-  h->st_cur = 0;
-  h->alpha_cur = 0;
-  h->d_dev = nullptr;
-  h->flag = nullptr;
-  h->steps_target = 0;
-  h->inv_sigma2 = 1.0;
-  h->lik_param2 = 1.0;
-  h->sigma_dirty = 1;
-  h->slots_per_step = 0.0;
-  h->slots_var = 0.0;
-  memset(&h->ctr, 0, sizeof h->ctr);
   Dev& d = h->d;
-  memset(&d, 0, sizeof d);
   d.n = s->n;
   d.nchunks = (int)((s->n + CH - 1) / CH);
   d.n_pad = (long long)d.nchunks * CH;
@@ -315,24 +331,10 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   d.ll_target = d.rows_target;
   d.compat = s->compat;
   if (const char* e = getenv("PGB_LL_TARGET")) d.ll_target = atoi(e) > 0 ? atoi(e) : d.ll_target;
-  // The likelihood pass is a persistent grid too, and its instances differ a lot in registers (probit 88
-  // VGPRs, K = 4 softmax 154): the grid is what the chosen instance can keep resident -- 5 workgroups per
-  // CU for probit, 3 for K = 4 -- so that no workgroup waits for another to finish; the pass aims for at
-  // least as many work items.  (cfg4: 1024 -> 1280 workgroups, k_loglik 40.3 -> 37.5 us.)
   h->ll_kernel = select_ll_kernel(d.K, d.response != PGB_RESPONSE_CONSTANT, d.family);
-  if (d.family != PGB_FAMILY_NORMAL && h->ll_kernel && !getenv("PGB_LL_GRID")) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h->ll_kernel, BT, 0) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0) {
-      // (K = 2, 3, 4: the instances are compiled for PGB_LLK_WGS workgroups per CU and measured best there --
-      //  cfg5: 768 workgroups 27.2-27.9 us, 1024 28.1-31.2 us, 1280 30.5-31.0 us -- whatever else would fit)
-      if (d.K >= 2 && d.K <= 4 && d.response == PGB_RESPONSE_CONSTANT && per_cu > PGB_LLK_WGS) per_cu = PGB_LLK_WGS;
-      long long g = (long long)per_cu * cus;
-      if (g < 256) g = 256;
-      if (g > 2048) g = 2048;
-      h->ll_grid = (int)g;
-      if (!getenv("PGB_LL_TARGET")) d.ll_target = h->ll_grid > 1024 ? h->ll_grid : 1024;
-    }
+  if (d.family != PGB_FAMILY_NORMAL && h->ll_kernel) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)h->ll_kernel, BT, 0) == hipSuccess) size_ll_grid(h, per_cu);
   }
   if (const char* e = getenv("PGB_ROWS_TARGET_INIT")) d.rows_target_init = atoi(e) > 0 ? atoi(e) : d.rows_target_init;
   // One launch per SMC round where the round is latency-bound: Normal likelihood, one output, constant
@@ -344,91 +346,79 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   d.mdouble = (double)s->m;
   d.sc = pgb_make_scales(s->n, s->range_exp);
   int rc;
-  double *XT, *y, *st, *rs_mean, *rs_m2, *prior_leaf;
-  long long *alpha, *cdfS;
-  double2* pack;
-  uint8_t *tree_lid, *lid;
-  uint16_t* cc;
-  int32_t *vi, *rules, *col_nan;
-#define DA(ptr, cnt) \
-  if ((rc = dalloc(h, &ptr, (size_t)(cnt))) != PGB_OK) { pgb_destroy(h); return rc; }
-  DA(XT, (size_t)d.p * d.n_pad);
-  DA(y, d.n_pad);
-  double* off;
-  DA(off, (size_t)d.K * d.n_pad);
-  d.off = off;
   const int K = d.K, KX = d.K - 1;
-  DA(st, (size_t)2 * K * d.n_pad);
-  DA(pack, d.n_pad);
-  DA(rs_mean, (size_t)K * d.n_pad);
-  DA(rs_m2, (size_t)K * d.n_pad);
+  const size_t n_pad = (size_t)d.n_pad, PN = (size_t)2 * MAXP * MAXN, MN = (size_t)d.m * MAXN, LV = 2 * 2 * 256;
+  // BUF(member, count [, fill [, value]]): one statement per buffer (dbuf); no fill = left as allocated
+#define BUF(...) \
+  if ((rc = dbuf(h, __VA_ARGS__)) != PGB_OK) { pgb_destroy(h); return rc; }
+  BUF(&d.XT, (size_t)d.p * n_pad);
+  BUF(&d.y, n_pad, FILL_ZERO);
+  BUF(&d.off, K * n_pad, FILL_ZERO);
+  BUF(&d.st, 2 * K * n_pad, FILL_F64, s->init_sum);
+  BUF(&d.pack, n_pad, FILL_ZERO);
+  BUF(&d.rs_mean, K * n_pad, FILL_ZERO);
+  BUF(&d.rs_m2, K * n_pad, FILL_ZERO);
   if (KX > 0) {  // K-vector leaves: extension outputs
-    DA(d.packx, (size_t)KX * d.n_pad);
-    DA(d.pvx, (size_t)2 * MAXP * MAXN * KX);
-    DA(d.pqx, (size_t)2 * MAXP * MAXN * KX);
-    DA(d.tvx, (size_t)d.m * MAXN * KX);
-    DA(d.accx, (size_t)2 * MAXP * AX_PER);
-    DA(d.iax, (size_t)2 * IA_SLOTS * 2 * KX);
-    DA(d.lvx, (size_t)2 * 2 * 256 * KX);
-    DA(d.jqx, (size_t)2 * MAXP * KX);
-    DA(d.jvx, (size_t)2 * MAXP * KX);
-    DA(d.jzx, (size_t)2 * MAXP * KX * 2);
-    DA(d.lsdx, (size_t)2 * KXMAX);
-    DA(d.finx, (size_t)2 * MAXP * KX);
+    BUF(&d.packx, KX * n_pad, FILL_ZERO);
+    BUF(&d.pvx, PN * KX, FILL_ZERO);
+    BUF(&d.pqx, PN * KX, FILL_ZERO);
+    BUF(&d.tvx, MN * KX, FILL_F64, s->init_leaf);  // every accepted tree starts as a stump whose K-vector leaf is init_leaf
+    BUF(&d.accx, (size_t)2 * MAXP * AX_PER, FILL_ZERO);
+    BUF(&d.iax, (size_t)2 * IA_SLOTS * 2 * KX, FILL_ZERO);
+    BUF(&d.lvx, LV * KX, FILL_ZERO);
+    BUF(&d.jqx, (size_t)2 * MAXP * KX, FILL_ZERO);
+    BUF(&d.jvx, (size_t)2 * MAXP * KX, FILL_ZERO);
+    BUF(&d.jzx, (size_t)2 * MAXP * KX * 2, FILL_ZERO);
+    BUF(&d.lsdx, (size_t)2 * KXMAX, FILL_F64, s->init_leaf_sd);
+    BUF(&d.finx, (size_t)2 * MAXP * KX, FILL_ZERO);
     if (s->family == PGB_FAMILY_CATEGORICAL && s->response == PGB_RESPONSE_CONSTANT) {
       // the row part of the factorised softmax: scratch of one tree update (no checkpoint carries it)
-      // (zeroed once below: the passes of a tree's later rounds read the padded rows of the last chunk as well, which
+      // (zeroed once here: the passes of a tree's later rounds read the padded rows of the last chunk as well, which
       //  the pass that starts the tree never writes)
-      DA(d.cat_e, (size_t)K * d.n_pad);
-      DA(d.cat_a, d.n_pad);
-      DA(d.cat_c, d.n_pad);
+      BUF(&d.cat_e, K * n_pad, FILL_ZERO);
+      BUF(&d.cat_a, n_pad, FILL_ZERO);
+      BUF(&d.cat_c, n_pad, FILL_ZERO);
     }
   }
-  DA(tree_lid, (size_t)d.m * d.n_pad);
-  DA(lid, (size_t)NGEN * MAXP * d.n_pad);
-  DA(cc, (size_t)CC_ROUNDS * MAXP * 2 * d.cc_stride);
+  BUF(&d.tree_lid, d.m * n_pad);  // (k_init_tree_lid below)
+  BUF(&d.lid, (size_t)NGEN * MAXP * n_pad, FILL_BYTE, PGB_ORPHAN);
+  BUF(&d.cc, (size_t)CC_ROUNDS * MAXP * 2 * d.cc_stride, FILL_ZERO);
   if (s->family == PGB_FAMILY_CALLBACK) {
-    DA(d.cb_mu, (size_t)MAXP * d.n_pad);
-    DA(d.cb_side, (size_t)MAXP * d.n_pad);
+    BUF(&d.cb_mu, MAXP * n_pad);
+    BUF(&d.cb_side, MAXP * n_pad);
     h->y_host.assign((size_t)d.n, 0.0);
     h->off_host.assign((size_t)d.n, 0.0);
   }
-  if (s->family == PGB_FAMILY_COMPILED) DA(h->cl_aux, d.n_pad);  // (zeroed below)
-  DA(d.trees, d.m);
-  DA(d.parts, 2 * MAXP);
-  DA(d.jobs, 2 * MAXP);
-  DA(d.acc, 2 * MAXP * ACC_PER);
-  DA(d.accl, 2 * MAXP * LL_PER);
-  DA(d.jobl, 2 * MAXP);
-  DA(d.initacc, 2 * IA_SLOTS);
-  DA(d.cmd, 2);
-  DA(d.ctrl, 2);
-  DA(d.counters, 8);
-  DA(vi, d.p);
-  DA(alpha, 2 * d.p);
-  DA(cdfS, 2 * d.p);
-  DA(prior_leaf, PGB_MAX_DEPTH);
-  DA(rules, d.p);
-  DA(col_nan, d.p);
-  int32_t* col_ex;
-  DA(col_ex, d.p);
-  d.col_ex = col_ex;
+  if (s->family == PGB_FAMILY_COMPILED) BUF(&h->cl_aux, n_pad, FILL_ZERO);
+  BUF(&d.trees, d.m);  // (k_init_trees below)
+  BUF(&d.parts, 2 * MAXP, FILL_ZERO);
+  BUF(&d.jobs, 2 * MAXP, FILL_ZERO);
+  BUF(&d.acc, 2 * MAXP * ACC_PER, FILL_ZERO);
+  BUF(&d.accl, 2 * MAXP * LL_PER, FILL_ZERO);
+  BUF(&d.jobl, 2 * MAXP, FILL_ZERO);
+  BUF(&d.initacc, 2 * IA_SLOTS, FILL_ZERO);
+  BUF(&d.cmd, 2, FILL_ZERO);
+  BUF(&d.ctrl, 2);  // (the idle control word below)
+  BUF(&d.counters, 8, FILL_ZERO);
+  BUF(&d.vi, d.p, FILL_ZERO);
+  BUF(&d.alpha, 2 * d.p);
+  BUF(&d.cdfS, 2 * d.p);
+  BUF(&d.prior_leaf, PGB_MAX_DEPTH);  // (copied from the settings below)
+  BUF(&d.rules, d.p);
+  BUF(&d.col_nan, d.p, FILL_ZERO);
+  BUF(&d.col_ex, d.p, FILL_ZERO);
   if (d.response != PGB_RESPONSE_CONSTANT) {
-    DA(d.plin, (size_t)2 * MAXP * MAXN);
-    DA(d.tlin, (size_t)d.m * MAXN);
-    DA(d.lvl, (size_t)2 * 2 * 256);
-    DA(d.accu, (size_t)2 * MAXP * ACC_PER);
+    BUF(&d.plin, PN, FILL_LINP);
+    BUF(&d.tlin, MN, FILL_LINP);
+    BUF(&d.lvl, LV, FILL_LINP);
+    BUF(&d.accu, (size_t)2 * MAXP * ACC_PER, FILL_ZERO);
     if (KX > 0) {
-      DA(d.psx, (size_t)2 * MAXP * MAXN * KX);
-      DA(d.tsx, (size_t)d.m * MAXN * KX);
-      DA(d.lsx, (size_t)2 * 2 * 256 * KX);
-      DA(d.accux, (size_t)2 * MAXP * AX_PER);
+      BUF(&d.psx, PN * KX, FILL_ZERO);
+      BUF(&d.tsx, MN * KX, FILL_ZERO);
+      BUF(&d.lsx, LV * KX, FILL_ZERO);
+      BUF(&d.accux, (size_t)2 * MAXP * AX_PER, FILL_ZERO);
     }
   }
-#undef DA
-  d.XT = XT; d.y = y; d.st = st; d.pack = pack; d.rs_mean = rs_mean; d.rs_m2 = rs_m2;
-  d.tree_lid = tree_lid; d.lid = lid; d.cc = cc; d.vi = vi; d.alpha = alpha; d.cdfS = cdfS;
-  d.rules = rules; d.col_nan = col_nan; d.prior_leaf = prior_leaf;
   hipStream_t sm = h->stream;
   hipError_t e;
 #define HC(expr) \
@@ -446,8 +436,7 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
     HC(hipHostGetDevicePointer(&dp, hp, 0));
     d.host_flag = (unsigned long long*)dp;
 #ifdef PGB_TRACE
-    if ((rc = dalloc(h, &d.trace, (size_t)TRACE_SLOTS * TRACE_W)) != PGB_OK) { pgb_destroy(h); return rc; }
-    HC(hipMemsetAsync(d.trace, 0, (size_t)TRACE_SLOTS * TRACE_W * sizeof(long long), sm));
+    BUF(&d.trace, (size_t)TRACE_SLOTS * TRACE_W, FILL_ZERO);
 #endif
     {  // host-facing results of pgb_step_host: mapped pinned block + dense sum_trees staging
       int cap_trees = s->batch_tune > s->batch_draw ? s->batch_tune : s->batch_draw;
@@ -460,65 +449,13 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
       void* dp2 = nullptr;
       HC(hipHostGetDevicePointer(&dp2, hp2, 0));
       h->out_dev = (unsigned char*)dp2;
-      if ((rc = dalloc(h, &h->st_dense, (size_t)d.K * d.n)) != PGB_OK) { pgb_destroy(h); return rc; }
+      BUF(&h->st_dense, (size_t)d.K * d.n);
     }
-    if ((rc = dalloc(h, &h->d_dev, 1)) != PGB_OK) { pgb_destroy(h); return rc; }
+    BUF(&h->d_dev, 1);
     HC(hipMemcpyAsync(h->d_dev, &d, sizeof(Dev), hipMemcpyHostToDevice, sm));
   }
-  HC(hipMemcpyAsync(prior_leaf, s->prior_leaf, PGB_MAX_DEPTH * sizeof(double), hipMemcpyHostToDevice, sm));
-  HC(hipMemsetAsync(y, 0, d.n_pad * sizeof(double), sm));
-  if (h->cl_aux) HC(hipMemsetAsync(h->cl_aux, 0, d.n_pad * sizeof(double), sm));
-  HC(hipMemsetAsync(off, 0, (size_t)d.K * d.n_pad * sizeof(double), sm));
-  HC(hipMemsetAsync(pack, 0, d.n_pad * sizeof(double2), sm));
-  HC(hipMemsetAsync(rs_mean, 0, (size_t)K * d.n_pad * sizeof(double), sm));
-  HC(hipMemsetAsync(rs_m2, 0, (size_t)K * d.n_pad * sizeof(double), sm));
-  if (KX > 0) {
-    HC(hipMemsetAsync(d.packx, 0, (size_t)KX * d.n_pad * sizeof(double), sm));
-    HC(hipMemsetAsync(d.pvx, 0, (size_t)2 * MAXP * MAXN * KX * sizeof(double), sm));
-    HC(hipMemsetAsync(d.pqx, 0, (size_t)2 * MAXP * MAXN * KX * sizeof(long long), sm));
-    HC(hipMemsetAsync(d.accx, 0, (size_t)2 * MAXP * AX_PER * sizeof(long long), sm));
-    HC(hipMemsetAsync(d.iax, 0, (size_t)2 * IA_SLOTS * 2 * KX * sizeof(long long), sm));
-    HC(hipMemsetAsync(d.lvx, 0, (size_t)2 * 2 * 256 * KX * sizeof(double), sm));
-    HC(hipMemsetAsync(d.jqx, 0, (size_t)2 * MAXP * KX * sizeof(long long), sm));
-    HC(hipMemsetAsync(d.jvx, 0, (size_t)2 * MAXP * KX * sizeof(double), sm));
-    HC(hipMemsetAsync(d.jzx, 0, (size_t)2 * MAXP * KX * 2 * sizeof(double), sm));
-    HC(hipMemsetAsync(d.finx, 0, (size_t)2 * MAXP * KX * sizeof(FinX), sm));
-    if (d.cat_e) {
-      HC(hipMemsetAsync(d.cat_e, 0, (size_t)K * d.n_pad * sizeof(double), sm));
-      HC(hipMemsetAsync(d.cat_a, 0, d.n_pad * sizeof(double), sm));
-      HC(hipMemsetAsync(d.cat_c, 0, d.n_pad, sm));
-    }
-    hipLaunchKernelGGL(k_fill_f64, dim3(1), dim3(256), 0, sm, d.lsdx, (long long)2 * KXMAX, s->init_leaf_sd);
-    // every accepted tree starts as a stump whose K-vector leaf is init_leaf
-    hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)(((size_t)d.m * MAXN * KX + 255) / 256)), dim3(256), 0, sm,
-                       d.tvx, (long long)d.m * MAXN * KX, s->init_leaf);
-  }
-  HC(hipMemsetAsync(lid, PGB_ORPHAN, (size_t)NGEN * MAXP * d.n_pad, sm));
-  HC(hipMemsetAsync(cc, 0, (size_t)CC_ROUNDS * MAXP * 2 * d.cc_stride * sizeof(uint16_t), sm));
-  HC(hipMemsetAsync(d.parts, 0, 2 * MAXP * sizeof(DPart), sm));
-  HC(hipMemsetAsync(d.jobs, 0, 2 * MAXP * sizeof(Job), sm));
-  HC(hipMemsetAsync(d.acc, 0, 2 * MAXP * ACC_PER * sizeof(Acc), sm));
-  HC(hipMemsetAsync(d.accl, 0, 2 * MAXP * LL_PER * sizeof(AccL), sm));
-  HC(hipMemsetAsync(d.jobl, 0, 2 * MAXP * sizeof(JobL), sm));
-  HC(hipMemsetAsync(d.initacc, 0, 2 * IA_SLOTS * sizeof(InitAcc), sm));
-  HC(hipMemsetAsync(d.cmd, 0, 2 * sizeof(Cmd), sm));
-  HC(hipMemsetAsync(d.counters, 0, 8 * sizeof(unsigned long long), sm));
-  HC(hipMemsetAsync(vi, 0, d.p * sizeof(int32_t), sm));
-  HC(hipMemsetAsync(col_nan, 0, d.p * sizeof(int32_t), sm));
-  HC(hipMemsetAsync(col_ex, 0, d.p * sizeof(int32_t), sm));
-  if (d.response != PGB_RESPONSE_CONSTANT) {
-    const long long n1 = (long long)2 * MAXP * MAXN, n2 = (long long)d.m * MAXN, n3 = 2 * 2 * 256;
-    hipLaunchKernelGGL(k_init_linp, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, sm, d.plin, n1);
-    hipLaunchKernelGGL(k_init_linp, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, sm, d.tlin, n2);
-    hipLaunchKernelGGL(k_init_linp, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, sm, d.lvl, n3);
-    HC(hipMemsetAsync(d.accu, 0, (size_t)2 * MAXP * ACC_PER * sizeof(AccU), sm));
-    if (KX > 0) {
-      HC(hipMemsetAsync(d.psx, 0, (size_t)2 * MAXP * MAXN * KX * sizeof(double), sm));
-      HC(hipMemsetAsync(d.tsx, 0, (size_t)d.m * MAXN * KX * sizeof(double), sm));
-      HC(hipMemsetAsync(d.lsx, 0, (size_t)2 * 2 * 256 * KX * sizeof(double), sm));
-      HC(hipMemsetAsync(d.accux, 0, (size_t)2 * MAXP * AX_PER * sizeof(long long), sm));
-    }
-  }
+#undef BUF
+  HC(hipMemcpyAsync((void*)d.prior_leaf, s->prior_leaf, PGB_MAX_DEPTH * sizeof(double), hipMemcpyHostToDevice, sm));
   Ctrl c0;
   memset(&c0, 0, sizeof c0);
   c0.phase = PH_IDLE;
@@ -527,15 +464,14 @@ extern "C" int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out)
   c0.lik_param2 = 1.0;
   Ctrl cc2[2] = {c0, c0};
   HC(hipMemcpyAsync(d.ctrl, cc2, sizeof cc2, hipMemcpyHostToDevice, sm));
-  hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)((2 * K * d.n_pad + 255) / 256)), dim3(256), 0, sm, st,
-                     2 * K * d.n_pad, s->init_sum);
   hipLaunchKernelGGL(k_init_tree_lid, dim3((unsigned)((d.n_pad * d.m + 255) / 256)), dim3(256), 0, sm,
-                     tree_lid, d.n, d.n_pad, d.m);
+                     d.tree_lid, d.n, d.n_pad, d.m);
   hipLaunchKernelGGL(k_init_trees, dim3((d.m + 63) / 64), dim3(64), 0, sm, d.trees, d.m, d.n,
                      s->init_leaf);
   HC(hipGetLastError());
   HC(hipStreamSynchronize(sm));
 #undef HC
+
   *out = h;
   return PGB_OK;
 }
@@ -571,14 +507,14 @@ static hipError_t order_keys_build(const double* XT, long long n, long long n_pa
   hipError_t e = hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, (const float*)nullptr, (float*)nullptr, (int)nn, 0, 32, sm);
   if (e != hipSuccess) return e;
   const size_t fl = (2 * nn + PGB_KEY_BOUNDS + 64) * sizeof(float);
-  char* scratch = nullptr;
-  e = hipMalloc((void**)&scratch, fl + tmp_bytes + 256);
+  DevBuf scratch;
+  e = hipMalloc((void**)&scratch.p, fl + tmp_bytes + 256);
   if (e != hipSuccess) return e;
-  float* staged = (float*)scratch;
+  float* staged = (float*)scratch.p;
   float* sorted = staged + nn;
   float* bnd = sorted + nn;
   unsigned* miss = (unsigned*)(bnd + PGB_KEY_BOUNDS);
-  void* tmp = scratch + fl;
+  void* tmp = scratch.p + fl;
   for (int c = 0; c < p && e == hipSuccess; ++c) {
     const double* col = XT + (size_t)c * n_pad;
     e = hipMemsetAsync(miss, 0, sizeof(unsigned), sm);
@@ -589,9 +525,7 @@ static hipError_t order_keys_build(const double* XT, long long n, long long n_pa
     hipLaunchKernelGGL(k_key_bounds, dim3(256), dim3(BT), 0, sm, (const float*)sorted, n, (const unsigned*)miss, bnd);
     hipLaunchKernelGGL(k_key_assign, dim3(2048), dim3(BT), 0, sm, col, (const float*)bnd, keys + (size_t)c * n_pad, n_pad);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(sm);
-  (void)hipFree(scratch);
-  return e;
+  return e == hipSuccess ? hipStreamSynchronize(sm) : e;
 }
 
 extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, const int32_t* rules_host,
@@ -603,15 +537,17 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
   Dev& d = h->d;
   if (ldx < d.p) return fail(PGB_E_INVALID, "ldx < p");
   double mx = 0.0;
-  h->has_subset = 0;
+  int has_subset = 0;
   for (int j = 0; j < d.p; ++j) {
-    if (rules_host[j] == PGB_RULE_SUBSET) h->has_subset = 1;
+    if (rules_host[j] == PGB_RULE_SUBSET) has_subset = 1;
     if (rules_host[j] != PGB_RULE_CONTINUOUS && rules_host[j] != PGB_RULE_ONEHOT &&
         rules_host[j] != PGB_RULE_SUBSET)
       return fail(PGB_E_UNSUPPORTED, "unknown split rule");
     if (!(split_prior_host[j] > 0.0)) return fail(PGB_E_INVALID, "split_prior must be positive");
     if (split_prior_host[j] > mx) mx = split_prior_host[j];
   }
+  if (has_subset != h->has_subset) h->slot_k = SlotKernels();  // (another instance of the row pass from here on)
+  h->has_subset = has_subset;
   d.max_prior = mx;
   d.alpha_unit = pgb_alpha_unit(mx);
   h->rules_host.assign(rules_host, rules_host + d.p);
@@ -625,17 +561,13 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
   hipLaunchKernelGGL(k_transpose, grid, dim3(BT), 0, sm, X_dev, (long long)ldx, (double*)d.XT, d.n,
                      d.n_pad, d.p, (int32_t*)d.col_nan);
   if (h->has_subset) {  // category codes outside 0 .. 51 are refused, not clamped (include/pgbart.h, Limits)
-    int* bad_dev = nullptr;
+    DevBuf bad_dev;
     int bad = 0;
-    HIPCHK(hipMalloc((void**)&bad_dev, sizeof(int)));
-    hipError_t e = hipMemsetAsync(bad_dev, 0, sizeof(int), sm);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_subset_check, dim3((unsigned)d.p), dim3(BT), 0, sm, d.XT, d.n, d.n_pad, (const int32_t*)d.rules, bad_dev);
-      e = hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, sm);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(sm);
-    (void)hipFree(bad_dev);
-    HIPCHK(e);
+    HIPCHK(hipMalloc((void**)&bad_dev.p, sizeof(int)));
+    HIPCHK(hipMemsetAsync(bad_dev.p, 0, sizeof(int), sm));
+    hipLaunchKernelGGL(k_subset_check, dim3((unsigned)d.p), dim3(BT), 0, sm, d.XT, d.n, d.n_pad, (const int32_t*)d.rules, (int*)bad_dev.p);
+    HIPCHK(hipMemcpyAsync(&bad, bad_dev.p, sizeof(int), hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipStreamSynchronize(sm));
     if (bad) {
       char msg[160];
       snprintf(msg, sizeof msg, "SubsetSplit column %d: categories must be integer codes in [0, %d) (NaN = missing)", bad - 1,
@@ -653,7 +585,7 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
     const size_t count = (size_t)d.p * d.n_pad;
     // THE predicate: keys are in use for this data or they are not -- whatever an earlier call decided
     const int use_keys = d.response == PGB_RESPONSE_CONSTANT && !h->has_subset && count * sizeof(double) >= min_bytes;
-    if (use_keys != h->use_keys) h->rows_mk_cap = 0;  // (another instance of the K-vector row pass from here on)
+    if (use_keys != h->use_keys) h->slot_k = SlotKernels();  // (the KEYS / F32 instances, or back, from here on)
     h->use_keys = use_keys;
     d.XK16 = nullptr;  // (the keys of an earlier matrix are ignored; the buffer stays for a later call that wants keys)
     if (use_keys) {
@@ -668,21 +600,20 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
       d.XK16 = h->xk16_buf;
     }
   }
-  double* prior_stage = nullptr;
+  DevBuf prior_stage;  // (released when the call returns: past the synchronisation below)
   if (d.p >= d.n_pad) {  // more columns than padded rows: stage through a temporary
-    HIPCHK(hipMalloc((void**)&prior_stage, d.p * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(prior_stage, split_prior_host, d.p * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMalloc((void**)&prior_stage.p, d.p * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(prior_stage.p, split_prior_host, d.p * sizeof(double), hipMemcpyHostToDevice, sm));
   }
-  hipLaunchKernelGGL(k_init_alpha, dim3(1), dim3(64), 0, sm, prior_stage ? prior_stage : d.rs_mean, mx,
+  hipLaunchKernelGGL(k_init_alpha, dim3(1), dim3(64), 0, sm, prior_stage.p ? (const double*)prior_stage.p : d.rs_mean, mx,
                      d.alpha, d.cdfS, d.p);
   if (d.response != PGB_RESPONSE_CONSTANT) {  // exponent bound of every column (u = x 2^-ex)
-    double* amax_dev = nullptr;
-    HIPCHK(hipMalloc((void**)&amax_dev, d.p * sizeof(double)));
-    hipLaunchKernelGGL(k_colmax, dim3((unsigned)d.p), dim3(BT), 0, sm, d.XT, d.n, d.n_pad, amax_dev);
+    DevBuf amax_dev;
+    HIPCHK(hipMalloc((void**)&amax_dev.p, d.p * sizeof(double)));
+    hipLaunchKernelGGL(k_colmax, dim3((unsigned)d.p), dim3(BT), 0, sm, d.XT, d.n, d.n_pad, (double*)amax_dev.p);
     std::vector<double> amax(d.p);
-    HIPCHK(hipMemcpyAsync(amax.data(), amax_dev, d.p * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipMemcpyAsync(amax.data(), amax_dev.p, d.p * sizeof(double), hipMemcpyDeviceToHost, sm));
     HIPCHK(hipStreamSynchronize(sm));
-    (void)hipFree(amax_dev);
     std::vector<int32_t> ex(d.p);
     for (int j = 0; j < d.p; ++j) ex[j] = pgb_col_exponent(amax[j]);
     HIPCHK(hipMemcpyAsync((void*)d.col_ex, ex.data(), d.p * sizeof(int32_t), hipMemcpyHostToDevice, sm));
@@ -692,7 +623,6 @@ extern "C" int pgb_set_data(pgb_handle* h, const double* X_dev, int64_t ldx, con
   HIPCHK(hipMemcpyAsync(h->d_dev, &d, sizeof(Dev), hipMemcpyHostToDevice, sm));  // alpha_unit, max_prior
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(sm));
-  if (prior_stage) (void)hipFree(prior_stage);
   h->have_data = 1;
   return PGB_OK;
 }
@@ -814,82 +744,66 @@ static int prof_events(pgb_handle* h, int k, hipEvent_t* e0, hipEvent_t* e1) {
 
 #include "pgb_compiled_host.h"
 
+// The instances of k_ctrl and of the row pass for a model and its data.  keys (pgb_set_data: constant leaves and no
+// SubsetSplit column) picks KEYS of k_ctrl and F32 of the row pass: always chosen together.
+static SlotKernels select_slot_kernels(int K, int P, bool lin, bool keys, bool sub, bool nrm) {
+  SlotKernels k;
+  k.ctrl_wgs = P - 1;
+  if (K > 1) {
+    // (statements, in this order: the instances are laid out in the code object in the order they are first named,
+    //  and k_ctrl is a latency kernel -- moving one to another alignment cost cfg5 0.8 %)
+    if (lin) k.ctrl = k_ctrl<true, true>;
+    else if (keys) k.ctrl = k_ctrl<true, false, true>;
+    else k.ctrl = k_ctrl<true, false>;
+    if (lin) k.rows = k_rows_mk<0, true>;  // linear leaves: one instance for any K
+    else if (K == 2) k.rows = keys ? k_rows_mk<2, false, true> : k_rows_mk<2, false>;
+    else if (K == 3) k.rows = keys ? k_rows_mk<3, false, true> : k_rows_mk<3, false>;
+    else if (K == 4) k.rows = keys ? k_rows_mk<4, false, true> : k_rows_mk<4, false>;
+    else k.rows = keys ? k_rows_mk<0, false, true> : k_rows_mk<0, false>;
+  } else if (lin) {  // (a linear leaf regresses on whatever column its parent split on)
+    k.ctrl = k_ctrl<false, true>;
+    if (sub) k.rows = nrm ? k_rows<true, true, true> : k_rows<true, false, true>;
+    else k.rows = nrm ? k_rows<false, true, true> : k_rows<false, false, true>;
+  } else {
+    k.ctrl = keys ? k_ctrl<false, false, true> : k_ctrl<false, false>;
+    k.ctrl_wgs = P;  // + the workgroup that builds the label tables ahead
+    if (sub) k.rows = nrm ? k_rows<true, true, false> : k_rows<true, false, false>;
+    else if (keys)  // 16-bit order keys of the split columns (matrix larger than the Infinity Cache)
+      k.rows = nrm ? k_rows<false, true, false, true> : k_rows<false, false, false, true>;
+    else k.rows = nrm ? k_rows<false, true, false> : k_rows<false, false, false>;
+  }
+  return k;
+}
+
 static int enqueue_slots(pgb_handle* h, int count) {
   Dev& d = h->d;
-  const bool lin = d.response != PGB_RESPONSE_CONSTANT;
-  const bool keys = h->use_keys != 0;  // KEYS of k_ctrl and F32 of the row pass: always chosen together (pgb_set_data)
-  long long want = (long long)d.nchunks * (d.P - 1);
-  if (want < d.n_pad / BT) want = d.n_pad / BT;
-  if (want > h->rows_grid) want = h->rows_grid;
-  if (d.K > 1) {
+  SlotKernels& sk = h->slot_k;
+  if (!sk.ctrl) {
+    sk = select_slot_kernels(d.K, d.P, d.response != PGB_RESPONSE_CONSTANT, h->use_keys != 0, h->has_subset != 0,
+                             h->s.family == PGB_FAMILY_NORMAL);
     // the K-vector instances differ in registers (K = 4: 3 workgroups per CU, the run-time-K instance 2-3): a
     // persistent grid larger than what stays resident leaves the surplus workgroups waiting for a first round of
     // items to finish (cfg5, in-kernel stamps: the last quarter of a 1024 grid started 22 us into a 27 us launch)
-    if (h->rows_mk_cap == 0) {
-      const bool f32 = h->use_keys != 0;
-      const void* kf = lin ? (const void*)k_rows_mk<0, true>
-                       : d.K == 2 ? (f32 ? (const void*)k_rows_mk<2, false, true> : (const void*)k_rows_mk<2, false>)
-                       : d.K == 3 ? (f32 ? (const void*)k_rows_mk<3, false, true> : (const void*)k_rows_mk<3, false>)
-                       : d.K == 4 ? (f32 ? (const void*)k_rows_mk<4, false, true> : (const void*)k_rows_mk<4, false>)
-                                  : (f32 ? (const void*)k_rows_mk<0, false, true> : (const void*)k_rows_mk<0, false>);
-      int per_cu = 0, cus = 0;
-      h->rows_mk_cap = h->rows_grid;
-      if (!getenv("PGB_ROWS_GRID") && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kf, BT, 0) == hipSuccess &&
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0)
-        h->rows_mk_cap = per_cu * cus < h->rows_grid ? per_cu * cus : h->rows_grid;
-    }
-    if (want > h->rows_mk_cap) want = h->rows_mk_cap;
+    int per_cu = 0, cus = 0;
+    sk.rows_cap = h->rows_grid;
+    if (d.K > 1 && !getenv("PGB_ROWS_GRID") &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)sk.rows, BT, 0) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && per_cu > 0 && cus > 0)
+      sk.rows_cap = per_cu * cus < h->rows_grid ? per_cu * cus : h->rows_grid;
   }
-  dim3 gctrl((unsigned)(d.P - 1)), grows((unsigned)want);
+  long long want = (long long)d.nchunks * (d.P - 1);
+  if (want < d.n_pad / BT) want = d.n_pad / BT;
+  if (want > sk.rows_cap) want = sk.rows_cap;
+  dim3 gctrl((unsigned)sk.ctrl_wgs), grows((unsigned)want);
   long long wantl = (long long)d.nchunks * (d.P - 1);
   if (wantl > h->ll_grid) wantl = h->ll_grid;
   dim3 gll((unsigned)wantl);
   const Dev* dd = (const Dev*)h->d_dev;
   for (int i = 0; i < count; ++i) {
     int par = (int)(h->slot & 1);
-#define CTRL_ARGS(nwg) dd, par, (int)(nwg), d.ctrl, (const InitAcc*)d.initacc, (const Job*)d.jobs, (const Acc*)d.acc, (const DPart*)d.parts, (const uint16_t*)d.XK16
-    if (d.K > 1 && lin) LAUNCH_K(PK_CTRL, (k_ctrl<true, true>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (d.K > 1 && keys) LAUNCH_K(PK_CTRL, (k_ctrl<true, false, true>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (d.K > 1) LAUNCH_K(PK_CTRL, (k_ctrl<true, false>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (lin) LAUNCH_K(PK_CTRL, (k_ctrl<false, true>), gctrl, CTRL_ARGS(gctrl.x));
-    else if (keys) LAUNCH_K(PK_CTRL, (k_ctrl<false, false, true>), dim3((unsigned)d.P), CTRL_ARGS(d.P));
-    else LAUNCH_K(PK_CTRL, (k_ctrl<false, false>), dim3((unsigned)d.P), CTRL_ARGS(d.P));  // + the workgroup that builds the label tables ahead
-#undef CTRL_ARGS
-#define ROWS_ARGS dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs
-    if (d.K > 1 && lin) {  // linear leaves: one instance for any K
-      LAUNCH_K(PK_ROWS, (k_rows_mk<0, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-    } else if (d.K == 2) {
-      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<2, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-      else LAUNCH_K(PK_ROWS, (k_rows_mk<2, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-    } else if (d.K == 3) {
-      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<3, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-      else LAUNCH_K(PK_ROWS, (k_rows_mk<3, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-    } else if (d.K == 4) {
-      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<4, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-      else LAUNCH_K(PK_ROWS, (k_rows_mk<4, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-    } else if (d.K > 1) {
-      if (keys) LAUNCH_K(PK_ROWS, (k_rows_mk<0, false, true>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-      else LAUNCH_K(PK_ROWS, (k_rows_mk<0, false>), grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
-    } else {
-      const bool nrm = h->s.family == PGB_FAMILY_NORMAL;
-      if (lin && h->has_subset) {  // (a linear leaf regresses on whatever column its parent split on)
-        if (nrm) LAUNCH_K(PK_ROWS, (k_rows<true, true, true>), grows, ROWS_ARGS);
-        else LAUNCH_K(PK_ROWS, (k_rows<true, false, true>), grows, ROWS_ARGS);
-      } else if (lin) {
-        if (nrm) LAUNCH_K(PK_ROWS, (k_rows<false, true, true>), grows, ROWS_ARGS);
-        else LAUNCH_K(PK_ROWS, (k_rows<false, false, true>), grows, ROWS_ARGS);
-      } else if (h->has_subset) {
-        if (nrm) LAUNCH_K(PK_ROWS, (k_rows<true, true, false>), grows, ROWS_ARGS);
-        else LAUNCH_K(PK_ROWS, (k_rows<true, false, false>), grows, ROWS_ARGS);
-      } else if (keys) {  // 16-bit order keys of the split columns (matrix larger than the Infinity Cache)
-        if (nrm) LAUNCH_K(PK_ROWS, (k_rows<false, true, false, true>), grows, ROWS_ARGS);
-        else LAUNCH_K(PK_ROWS, (k_rows<false, false, false, true>), grows, ROWS_ARGS);
-      } else {
-        if (nrm) LAUNCH_K(PK_ROWS, (k_rows<false, true, false>), grows, ROWS_ARGS);
-        else LAUNCH_K(PK_ROWS, (k_rows<false, false, false>), grows, ROWS_ARGS);
-      }
-    }
-#undef ROWS_ARGS
+    LAUNCH_K(PK_CTRL, sk.ctrl, gctrl, dd, par, sk.ctrl_wgs, d.ctrl, (const InitAcc*)d.initacc, (const Job*)d.jobs,
+             (const Acc*)d.acc, (const DPart*)d.parts, (const uint16_t*)d.XK16);
+    LAUNCH_K(PK_ROWS, sk.rows, grows, dd, par, (const Cmd*)d.cmd, (const Job*)d.jobs);
     if (d.family == PGB_FAMILY_COMPILED) {  // (the module kernel of pgb_set_loglik_code)
       const int rc_ = compiled_launch(h, par, (int)gll.x);
       if (rc_ != PGB_OK) return rc_;
@@ -901,6 +815,7 @@ static int enqueue_slots(pgb_handle* h, int count) {
   HIPCHK(hipGetLastError());
   return PGB_OK;
 }
+
 
 static int harvest_profile(pgb_handle* h) {
   for (int k = 0; k < PK_COUNT; ++k) {
@@ -1009,6 +924,37 @@ static double watchdog_seconds() {
   static const double v = getenv("PGB_WATCHDOG_S") ? atof(getenv("PGB_WATCHDOG_S")) : 20.0;
   return v > 0.1 ? v : 0.1;
 }
+// Lost-device watchdog by the WALL clock (a poll count means different times on different hosts, and a false
+// trip poisons the chain): PGB_WATCHDOG_S seconds without a single slot starting (flag[2]); the deadline MOVES
+// whenever the device publishes progress, so that a pass that takes longer than PGB_WATCHDOG_S on a time-sliced GPU,
+// under a profiler or at very large n does not poison a healthy chain (round-4 ADVICE).  A device that stops
+// publishing progress (lost GPU, a kernel that faulted) ends the call, not the process: poll() looks at the clock
+// every 0x4000 calls and, past the deadline, poisons the handle and fails with the caller's sentence for a stream
+// in error (`lost`) or for a healthy but stuck one (`stuck`).
+struct ProgressWatch {
+  pgb_handle* h;
+  const char *lost, *stuck;
+  long long polls = 0, seen;
+  std::chrono::steady_clock::time_point deadline;
+  static std::chrono::steady_clock::time_point after(std::chrono::steady_clock::time_point now) {
+    return now + std::chrono::milliseconds((long long)(watchdog_seconds() * 1e3));
+  }
+  ProgressWatch(pgb_handle* h_, const char* lost_, const char* stuck_)
+      : h(h_), lost(lost_), stuck(stuck_), seen((long long)h_->flag[2]), deadline(after(std::chrono::steady_clock::now())) {}
+  bool expired(std::chrono::steady_clock::time_point now) {
+    if ((long long)h->flag[2] == seen) return now > deadline;
+    seen = (long long)h->flag[2];
+    deadline = after(now);
+    return false;
+  }
+  int poll() {
+    if ((++polls & 0x3FFF) != 0 || !expired(std::chrono::steady_clock::now())) return PGB_OK;
+    hipError_t e = hipStreamQuery(h->stream);
+    h->poisoned = 1;
+    if (e != hipSuccess && e != hipErrorNotReady) return fail_hip(e, lost);
+    return fail(PGB_E_STATE, stuck);
+  }
+};
 #define FEED_AHEAD 24
 #define FEED_MIN 6
 #define FEED_RUN 8
@@ -1044,13 +990,8 @@ static int feed_until_flag(pgb_handle* h, int n_steps) {
     double e = h->slots_per_step * n_steps - feed_sd * sd * __builtin_sqrt((double)n_steps);
     expect_end = start + (long long)(e > 1.0 ? e : 1.0);
   }
-  long long idle_polls = 0;
   int refill = 0;
-  // lost-device watchdog by the WALL clock (a poll count means different times on different hosts, and a false
-  // trip poisons the chain): PGB_WATCHDOG_S seconds without a single slot starting; the deadline moves whenever
-  // the device publishes progress
-  long long seen = (long long)h->flag[2];
-  auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds((long long)(watchdog_seconds() * 1e3));
+  ProgressWatch watch(h, "device stopped making progress", "device stopped publishing slot progress");
   while (*h->flag < (unsigned long long)h->steps_target) {
     const long long executed = (long long)h->flag[2];
     long long limit = executed + feed_ahead;
@@ -1070,26 +1011,14 @@ static int feed_until_flag(pgb_handle* h, int n_steps) {
         h->poisoned = 1;
         return fail(PGB_E_STATE, "sampler state machine did not finish");
       }
-      idle_polls = 0;
+      watch.polls = 0;  // (idle polls since the last slot went out)
     } else {
       refill = 0;
       for (int i = 0; i < 16; ++i) __builtin_ia32_pause();
       // several chains feed their own streams from their own threads (chains.sample_chains, bench.py's
       // concurrent chains): a waiting feeder gives its core away instead of spinning against the others
       if (g_live_handles.load(std::memory_order_relaxed) > 1) sched_yield();
-      // a device that stops publishing progress (lost GPU, a kernel that faulted) ends the call, not the process
-      if ((++idle_polls & 0x3FFF) == 0) {
-        const auto now = std::chrono::steady_clock::now();
-        if ((long long)h->flag[2] != seen) {
-          seen = (long long)h->flag[2];
-          deadline = now + std::chrono::milliseconds((long long)(watchdog_seconds() * 1e3));
-        } else if (now > deadline) {
-          hipError_t e = hipStreamQuery(h->stream);
-          h->poisoned = 1;
-          if (e != hipSuccess && e != hipErrorNotReady) return fail_hip(e, "device stopped making progress");
-          return fail(PGB_E_STATE, "device stopped publishing slot progress");
-        }
-      }
+      if ((rc = watch.poll()) != PGB_OK) return rc;
     }
   }
   return PGB_OK;
@@ -1109,11 +1038,18 @@ static int run_until_idle(pgb_handle* h, int n_steps) {
   return PGB_OK;
 }
 
-static int begin_steps(pgb_handle* h, int tune, int n_steps) {
-  Dev& d = h->d;
+// what a step needs: data and response, a chain whose state is defined, the compiled family's code
+static int check_can_step(pgb_handle* h) {
   if (!h->have_data || !h->have_y) return fail(PGB_E_INVALID, "set_data/set_response first");
   REFUSE_POISONED(h);
   if (h->s.family == PGB_FAMILY_COMPILED && !h->cl_fn) return fail(PGB_E_INVALID, "pgb_set_loglik_code first");
+  return PGB_OK;
+}
+
+static int begin_steps(pgb_handle* h, int tune, int n_steps) {
+  Dev& d = h->d;
+  const int rc = check_can_step(h);
+  if (rc != PGB_OK) return rc;
   int par = (int)(h->slot & 1);
   h->out_valid = 0;
   hipLaunchKernelGGL(k_begin, dim3(1), dim3(256), 0, h->stream, h->d_dev, par, tune, n_steps,
@@ -1225,26 +1161,11 @@ extern "C" int pgb_step_host(pgb_handle* h, int32_t tune, double* sum_trees_host
   const bool early = h->s.family != PGB_FAMILY_CALLBACK && !h->prof && h->stream_out != nullptr;
   if (early) {
     int extra = 0;
-    long long polls = 0;
-    auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds((long long)(watchdog_seconds() * 1e3));
-    long long seen2 = (long long)h->flag[2];
+    ProgressWatch watch(h, "device stopped before the step-complete word", "the step-complete word never fired");
     while (h->flag[1] < (unsigned long long)h->steps_target) {
       // (a device that faults between "last tree accepted" and the first idle slot would otherwise hold this
-      //  loop for ever, with the GIL released.  As in feed_until_flag the deadline MOVES while the device
-      //  publishes progress -- slots starting -- so that a FINAL pass that takes longer than PGB_WATCHDOG_S on a
-      //  time-sliced GPU, under a profiler or at very large n does not poison a healthy chain: round-4 ADVICE)
-      if ((++polls & 0x3FFF) == 0) {
-        const auto now = std::chrono::steady_clock::now();
-        if ((long long)h->flag[2] != seen2) {
-          seen2 = (long long)h->flag[2];
-          deadline = now + std::chrono::milliseconds((long long)(watchdog_seconds() * 1e3));
-        } else if (now > deadline) {
-          hipError_t e = hipStreamQuery(h->stream);
-          h->poisoned = 1;
-          if (e != hipSuccess && e != hipErrorNotReady) return fail_hip(e, "device stopped before the step-complete word");
-          return fail(PGB_E_STATE, "the step-complete word never fired");
-        }
-      }
+      //  loop for ever, with the GIL released; a long FINAL pass moves the deadline like any other progress)
+      if ((rc = watch.poll()) != PGB_OK) return rc;
       // every enqueued slot has started and none of them was an idle one behind the finishing slot: one more
       if ((long long)h->flag[2] >= h->slot) {
         if (h->flag[1] >= (unsigned long long)h->steps_target) break;
@@ -1293,9 +1214,8 @@ extern "C" int pgb_step_host(pgb_handle* h, int32_t tune, double* sum_trees_host
 extern "C" int pgb_step_async(pgb_handle* h, int32_t tune, int32_t n_steps) {
   if (!h || n_steps < 1) return fail(PGB_E_INVALID, "bad argument");
   JOIN_ASYNC(h);
-  if (!h->have_data || !h->have_y) return fail(PGB_E_INVALID, "set_data/set_response first");
-  REFUSE_POISONED(h);
-  if (h->s.family == PGB_FAMILY_COMPILED && !h->cl_fn) return fail(PGB_E_INVALID, "pgb_set_loglik_code first");
+  const int rc0 = check_can_step(h);  // (refused here, synchronously, not in the worker)
+  if (rc0 != PGB_OK) return rc0;
   h->job_running = 1;
   h->job_rc = PGB_OK;
   h->job_err[0] = 0;
@@ -1362,77 +1282,123 @@ static int export_from_block(pgb_handle* h, pgb_tree_arrays* out) {
   return PGB_OK;
 }
 
+// Accepted trees [first, first + nt) in host memory: the node tables, and where the model has them the K-vector
+// values (tvx), the linear leaves (tlin) and the slopes of outputs 1..K-1 (tsx).  The accessors state once how a
+// node's fields follow from them; write_nodes() turns them into the flat node arrays of the chain image and of
+// pgb_tree_arrays (host arrays in, host arrays out: no device involved).
+struct HostTrees {
+  int first = 0, nt = 0, K = 1;
+  std::vector<DTree> T;
+  std::vector<double> vx, sx;  // [nt][MAXN][K - 1]
+  std::vector<LinP> lin;       // [nt][MAXN]; empty: constant leaves, or not fetched
+  const DNode& node(int t, int k) const { return T[t].nd[k]; }
+  size_t at(int t, int k, int o) const { return ((size_t)t * MAXN + k) * (K - 1) + o - 1; }
+  int total_nodes() const {
+    int N = 0;
+    for (int t = 0; t < nt; ++t) N += T[t].n_nodes;
+    return N;
+  }
+  double value(int t, int k, int o) const { return node(t, k).var >= 0 ? 0.0 : o ? vx[at(t, k, o)] : node(t, k).value; }
+  bool is_lin(int t, int k) const { return node(t, k).var < 0 && !lin.empty() && lin[(size_t)t * MAXN + k].svar >= 0; }
+  double slope(int t, int k, int o) const { return !is_lin(t, k) ? 0.0 : o ? sx[at(t, k, o)] : lin[(size_t)t * MAXN + k].slope; }
+  double xbar(int t, int k) const { return is_lin(t, k) ? lin[(size_t)t * MAXN + k].xbar : 0.0; }
+  int32_t svar(int t, int k) const { return is_lin(t, k) ? (int32_t)lin[(size_t)t * MAXN + k].svar : -1; }
+
+  // the node tables: every enqueued slot has run once the stream is idle; blocking copies from there
+  int fetch(pgb_handle* h, int first_, int nt_) {
+    first = first_, nt = nt_, K = h->d.K;
+    T.resize((size_t)nt);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (nt > 0) HIPCHK(hipMemcpy(T.data(), h->d.trees + first, sizeof(DTree) * nt, hipMemcpyDeviceToHost));
+    return PGB_OK;
+  }
+  // ... and the leaf parts next to them (want_lin = false: a caller that takes no slopes)
+  int fetch_leaves(pgb_handle* h, bool want_lin) {
+    const Dev& d = h->d;
+    const size_t nodes = (size_t)nt * MAXN, KX = (size_t)(K - 1);
+    if (nt <= 0) return PGB_OK;
+    if (KX > 0) {
+      vx.resize(nodes * KX);
+      HIPCHK(hipMemcpy(vx.data(), d.tvx + (size_t)first * MAXN * KX, vx.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (!want_lin || d.response == PGB_RESPONSE_CONSTANT) return PGB_OK;
+    lin.resize(nodes);
+    HIPCHK(hipMemcpy(lin.data(), d.tlin + (size_t)first * MAXN, lin.size() * sizeof(LinP), hipMemcpyDeviceToHost));
+    if (KX > 0) {
+      sx.resize(nodes * KX);
+      HIPCHK(hipMemcpy(sx.data(), d.tsx + (size_t)first * MAXN * KX, sx.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return PGB_OK;
+  }
+};
+
+// where the flat node arrays go: the fields the image and pgb_tree_arrays share, and the two only the image has
+struct NodeSink {
+  int32_t *node_off, *var, *left, *right;
+  int64_t* count;
+  double *split, *value;
+  double* slope;  // with xbar and svar, or all three null: no linear part wanted
+  double* xbar;
+  int32_t* svar;
+  int32_t *depth, *label;  // (null: pgb_tree_arrays)
+};
+static NodeSink node_sink(const pgb_image_view& v) {
+  return NodeSink{v.node_off, v.var, v.left, v.right, v.count, v.split, v.value, v.slope, v.xbar, v.svar, v.depth, v.label};
+}
+static NodeSink node_sink(const pgb_tree_arrays* a) {
+  const bool want_lin = a->slope && a->xbar && a->svar;
+  return NodeSink{a->node_off, a->var, a->left, a->right, a->count, a->split, a->value, want_lin ? a->slope : nullptr,
+                  want_lin ? a->xbar : nullptr, want_lin ? a->svar : nullptr, nullptr, nullptr};
+}
+static void write_nodes(const HostTrees& ht, const NodeSink& out) {
+  const int K = ht.K;
+  int32_t g = 0;
+  for (int t = 0; t < ht.nt; ++t) {
+    out.node_off[t] = g;
+    for (int k = 0; k < ht.T[t].n_nodes; ++k, ++g) {
+      const DNode& z = ht.node(t, k);
+      const bool leaf = z.var < 0;
+      out.var[g] = z.var;
+      out.split[g] = leaf ? 0.0 : z.split;
+      out.left[g] = leaf ? -1 : (int32_t)z.left;
+      out.right[g] = leaf ? -1 : (int32_t)z.right;
+      out.count[g] = z.cnt;
+      for (int o = 0; o < K; ++o) out.value[(size_t)g * K + o] = ht.value(t, k, o);
+      if (out.slope) {
+        for (int o = 0; o < K; ++o) out.slope[(size_t)g * K + o] = ht.slope(t, k, o);
+        out.xbar[g] = ht.xbar(t, k);
+        out.svar[g] = ht.svar(t, k);
+      }
+      if (out.depth) out.depth[g] = z.depth, out.label[g] = z.label;
+    }
+  }
+  out.node_off[ht.nt] = g;
+}
+
 extern "C" int pgb_export_trees(pgb_handle* h, int32_t which, pgb_tree_arrays* out) {
   if (!h || !out) return fail(PGB_E_INVALID, "null argument");
   JOIN_ASYNC(h);
   REFUSE_POISONED(h);
-  Dev& d = h->d;
   if (which == 0 && h->out_valid) return export_from_block(h, out);
-  int first = which == 0 ? h->last_lower : 0;
-  int nt = which == 0 ? h->last_n : d.m;
-  std::vector<DTree> host(nt);
-  if (nt > 0) {
-    HIPCHK(hipMemcpyAsync(host.data(), d.trees + first, sizeof(DTree) * nt, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  int total = 0;
-  for (int t = 0; t < nt; ++t) total += host[t].n_nodes;
-  const int K = d.K, KX = d.K - 1;
+  HostTrees ht;
+  int rc = ht.fetch(h, which == 0 ? h->last_lower : 0, which == 0 ? h->last_n : h->d.m);
+  if (rc != PGB_OK) return rc;
+  const int total = ht.total_nodes();
   if (!out->var) {
-    out->n_trees = nt;
-    out->n_outputs = K;
+    out->n_trees = ht.nt;
+    out->n_outputs = ht.K;
     out->total_nodes = total;
     return PGB_OK;
   }
-  std::vector<double> hx;
-  if (KX > 0 && nt > 0) {
-    hx.resize((size_t)nt * MAXN * KX);
-    HIPCHK(hipMemcpy(hx.data(), d.tvx + (size_t)first * MAXN * KX, hx.size() * sizeof(double),
-                     hipMemcpyDeviceToHost));
-  }
-  if (out->n_trees != nt || out->total_nodes != total) return fail(PGB_E_INVALID, "size mismatch");
-  std::vector<LinP> hl;
-  std::vector<double> hsx;  // slopes of outputs 1..K-1
-  const bool want_lin = out->slope && out->xbar && out->svar;
-  if (want_lin && d.response != PGB_RESPONSE_CONSTANT && nt > 0) {
-    hl.resize((size_t)nt * MAXN);
-    HIPCHK(hipMemcpy(hl.data(), d.tlin + (size_t)first * MAXN, hl.size() * sizeof(LinP), hipMemcpyDeviceToHost));
-    if (KX > 0) {
-      hsx.resize((size_t)nt * MAXN * KX);
-      HIPCHK(hipMemcpy(hsx.data(), d.tsx + (size_t)first * MAXN * KX, hsx.size() * sizeof(double),
-                       hipMemcpyDeviceToHost));
-    }
-  }
-  int off = 0;
-  for (int t = 0; t < nt; ++t) {
-    const DTree& T = host[t];
-    out->tree_id[t] = first + t;
-    out->node_off[t] = off;
-    for (int k = 0; k < T.n_nodes; ++k) {
-      const DNode& z = T.nd[k];
-      out->var[off + k] = z.var;
-      out->split[off + k] = z.var >= 0 ? z.split : 0.0;
-      out->left[off + k] = z.var >= 0 ? (int32_t)z.left : -1;
-      out->right[off + k] = z.var >= 0 ? (int32_t)z.right : -1;
-      out->count[off + k] = z.cnt;
-      out->value[(size_t)(off + k) * K] = z.var < 0 ? z.value : 0.0;
-      if (want_lin) {
-        const bool islin = z.var < 0 && !hl.empty() && hl[(size_t)t * MAXN + k].svar >= 0;
-        out->slope[(size_t)(off + k) * K] = islin ? hl[(size_t)t * MAXN + k].slope : 0.0;
-        for (int o = 1; o < K; ++o)
-          out->slope[(size_t)(off + k) * K + o] = islin ? hsx[((size_t)t * MAXN + k) * KX + o - 1] : 0.0;
-        out->xbar[off + k] = islin ? hl[(size_t)t * MAXN + k].xbar : 0.0;
-        out->svar[off + k] = islin ? (int32_t)hl[(size_t)t * MAXN + k].svar : -1;
-      }
-      for (int o = 1; o < K; ++o)
-        out->value[(size_t)(off + k) * K + o] = z.var < 0 ? hx[((size_t)t * MAXN + k) * KX + o - 1] : 0.0;
-    }
-    off += T.n_nodes;
-  }
-  out->node_off[nt] = off;
+  if (out->n_trees != ht.nt || out->total_nodes != total) return fail(PGB_E_INVALID, "size mismatch");
+  const NodeSink sink = node_sink(out);
+  if ((rc = ht.fetch_leaves(h, sink.slope != nullptr)) != PGB_OK) return rc;
+  for (int t = 0; t < ht.nt; ++t) out->tree_id[t] = ht.first + t;
+  write_nodes(ht, sink);
   fill_node_rules(h, out, total);
   return PGB_OK;
 }
+
 
 extern "C" int pgb_export_trees_packed(pgb_handle* h, int32_t which, void* host_buf, int64_t cap_bytes,
                                        int64_t* bytes_out) {

@@ -132,17 +132,6 @@ static int pred_validate(const pgb_tree_arrays* trees, const int32_t* forest_tre
   return PGB_OK;
 }
 
-// one device buffer of a call, released on every way out
-struct DevBuf {
-  uint8_t* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // ... and packed into ONE upload (db: owned, released with the pack) for the walk of pgb_pred_walk.h
 struct PredPack {
   uint8_t* db = nullptr;

@@ -19,6 +19,7 @@ from .shap_interaction import shap_interaction_summary, shap_interaction_values
 from .pointwise import log_predictive_density, pointwise_log_likelihood
 from .loo import loo, loo_pit, loo_predictive, psis_expectation_matrix, psis_loo_matrix
 from .summary import posterior_summary, summarize_matrix
+from .diagnostics import convergence, diagnose_matrix, relative_efficiency
 from .predictive import posterior_predictive, predictive_pit, predictive_summary
 
 
@@ -42,6 +43,6 @@ __version__ = "0.1.0"
 __all__ = [
     "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
-    "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix",
+    "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix", "convergence", "diagnose_matrix", "relative_efficiency",
     "posterior_predictive", "predictive_summary", "predictive_pit", "shap_values", "shap_summary", "shap_interaction_values", "shap_interaction_summary", "_abi",
 ]

@@ -345,6 +345,18 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def chain_diag_entry_point(self):
+        """``pgb_chain_diag`` (include/pgbart_diag.h): HIP library only, hence not in SYMBOLS.  A library without the
+        symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_chain_diag
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_chain_diag (HIP library only)") from None
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     def ppc_entry_point(self):
         """``pgb_ppc_draw`` (include/pgbart_ppc.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_ppc_draw

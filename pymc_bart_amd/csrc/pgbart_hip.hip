@@ -51,6 +51,7 @@
 #include "pgbart_psis.h"
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
+#include "pgbart_diag.h"
 #include "pgbart_ppc.h"
 #include "pgbart_shap.h"
 
@@ -76,6 +77,7 @@
 #include "k_psis.h"
 #include "k_ice.h"
 #include "k_rowsummary.h"
+#include "k_diag.h"
 #include "k_ppc.h"
 #include "k_pdp.h"
 #include "k_shap.h"

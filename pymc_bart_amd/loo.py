@@ -14,7 +14,8 @@ says whether the row's estimate can be trusted.  The numeric contract is ``inclu
   host.  :func:`psis_expectation_matrix` does the same for two ``(D, n)`` matrices held on the host.
 
 HIP backend only.  At most :data:`MAX_DRAWS` draws, and a tail of at most :data:`MAX_TAIL` (reached only by a small
-``reff`` with thousands of draws); ``reff`` is the caller's (1.0: independent draws).
+``reff`` with thousands of draws); ``reff`` is the caller's (1.0: independent draws;
+:func:`~pymc_bart_amd.relative_efficiency` computes it from the chains).
 """
 
 from __future__ import annotations

@@ -134,17 +134,21 @@ class _Job:
         self.fidx = np.ascontiguousarray(np.asarray(table)[idx], dtype=np.int32)
         self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None
 
-    def run(self, keep_matrix: bool = False):
+    def run(self, keep_matrix: bool = False, on_block=None, out_rows: int = 0):
         """-> (the public dict, the predictions ``(D, K, n)`` or None).  ``keep_matrix``: also copy every block's
-        predictions to the host (partial dependence returns them next to their summary)."""
+        predictions to the host (partial dependence returns them next to their summary).  ``on_block(lib, mem, md,
+        n_cols, od)``: another second kernel on every block's predictions ``md`` ``[D][n_cols]`` in place of
+        ``pgb_row_summary`` (:mod:`pymc_bart_amd.diagnostics`); it returns ``(out_rows, n_cols)`` and the first result
+        is then the array ``(out_rows, K, n)`` itself."""
         from .sampler import default_backend
 
         be = _hip(self.backend() if self.backend is not None else default_backend())
         lib, mem = be.lib, be.mem
         n, D, K, p, Q = self.n, self.D, self.K, self.p, self.q.size
-        per_row = 8 * (p + K * (D + 1 + 2 + Q + 2))
+        rows = 2 + Q + 2 if on_block is None else int(out_rows)
+        per_row = 8 * (p + K * (D + 1 + rows))
         block = max(64, min(n, _block_bytes() // per_row // 64 * 64))
-        stats = np.empty((2 + Q + 2, K, n))
+        stats = np.empty((rows, K, n))
         pred = np.empty((D, K, n)) if keep_matrix else None
         carr = self.pool.as_c()
         excl = self.excluded
@@ -157,10 +161,15 @@ class _Job:
             rc = lib.lib.pgb_predict(C.byref(carr), self.fidx.ctypes.data, D, self.m, mem.ptr(xd), nb, p, p,
                                      excl.ctypes.data if excl.size else None, int(excl.size), mem.ptr(md), mem.stream_ptr)
             lib.check(rc, "pgb_predict")
-            stats[:, :, r0:r1] = _summary_block(lib, mem, md, D, K * nb, K * nb, od, self.code, self.q,
-                                                self.hdi_k).reshape(-1, K, nb)
+            if on_block is None:
+                blk = _summary_block(lib, mem, md, D, K * nb, K * nb, od, self.code, self.q, self.hdi_k)
+            else:
+                blk = on_block(lib, mem, md, K * nb, od)
+            stats[:, :, r0:r1] = blk.reshape(-1, K, nb)
             if keep_matrix:
                 pred[:, :, r0:r1] = mem.to_host(md).reshape(D, K, nb)
+        if on_block is not None:
+            return stats, pred
         return _result(stats, n, K, self.q, self.hdi_prob, self.hdi_k, D), pred
 
 

@@ -23,8 +23,9 @@ from statistics import NormalDist
 
 import numpy as np
 
-from . import _abi
-from .pointwise import _block_bytes, _chains
+from ._stored import chains, hip_only, matrix_blocks
+from .pointwise import ScoringJob
+from .summary import SummaryJob
 
 MAX_DRAWS = 8192        # PGB_DIAG_MAX_DRAWS (include/pgbart_diag.h)
 MAX_DRAWS_MEAN = 16384  # PGB_DIAG_MAX_DRAWS_MEAN
@@ -62,15 +63,6 @@ def kept_draws(n_chains: int, n_per_chain: int, stats: int = ALL) -> int:
         raise ValueError(f"chain diagnostics on the device take at most {cap} draws after the split, got {S} "
                          f"({n_chains} chains x {n_per_chain}; thin them: draws_per_chain=)")
     return S
-
-
-def _hip(backend):
-    from .sampler import default_backend
-
-    be = backend if backend is not None else default_backend()
-    if be.lib.backend_name != "hip-gfx950":
-        raise _abi.PGBError(f"chain diagnostics run on the HIP backend only, not on {be.lib.backend_name}")
-    return be
 
 
 def _diag_block(lib, mem, md, n_chains: int, n_per_chain: int, n_cols: int, ld: int, code: int, stats: int) -> np.ndarray:
@@ -117,20 +109,16 @@ def diagnose_matrix(a, n_chains: int, transform: str = "identity", backend=None)
     kept_draws(n_chains, npc)
     if not np.all(np.isfinite(a)):
         raise ValueError("a must be finite")
-    be = _hip(backend)
-    lib, mem = be.lib, be.mem
-    block = max(64, min(n, _block_bytes() // (8 * (D + NOUT)) // 64 * 64))
+    be = hip_only(backend, "chain diagnostics run")
     stats = np.empty((NOUT, n))
-    for r0 in range(0, n, block):
-        r1 = min(n, r0 + block)
-        md = mem.from_host(np.ascontiguousarray(a[:, r0:r1]))
-        stats[:, r0:r1] = _diag_block(lib, mem, md, n_chains, npc, r1 - r0, r1 - r0, TRANSFORMS[transform], ALL)
+    for r0, r1, md in matrix_blocks(be, 8 * (D + NOUT), a):
+        stats[:, r0:r1] = _diag_block(be.lib, be.mem, md, n_chains, npc, r1 - r0, r1 - r0, TRANSFORMS[transform], ALL)
     return _public(stats, n_chains, npc)
 
 
 def _chain_draws(sampler, draws_per_chain, stats: int):
     """-> (indexes of the stored draws, chain-major; n_chains; n_per_chain) of the sampler's own chains."""
-    lengths = [int(part.forest_idx.shape[0]) for part in _chains(sampler)]
+    lengths = [int(part.forest_idx.shape[0]) for part in chains(sampler)]
     if draws_per_chain is None:
         if len(set(lengths)) != 1:
             raise ValueError(f"the chains hold {lengths} draws: chains of unequal length need draws_per_chain= "
@@ -161,12 +149,11 @@ def convergence(sampler, X, draws_per_chain=None, transform: str = "identity", o
     if transform != "identity":
         raise ValueError(f"convergence takes transform='identity' only for now, not {transform!r}")
     idx, n_chains, npc = _chain_draws(sampler, draws_per_chain, ALL)
-    from .summary import _Job
+    job = SummaryJob(sampler, X, idx, None, None, "identity", offset, excluded)
 
-    job = _Job(sampler, X, idx, None, None, "identity", offset, excluded)
-
-    def diag(lib, mem, md, n_cols, od):
-        return _diag_block(lib, mem, md, n_chains, npc, n_cols, n_cols, TRANSFORMS["identity"], ALL)
+    def diag(be, blk):
+        n_cols = job.K * blk.nb
+        return _diag_block(be.lib, be.mem, blk.md, n_chains, npc, n_cols, n_cols, TRANSFORMS["identity"], ALL)
 
     stats, _ = job.run(on_block=diag, out_rows=NOUT)                            # (NOUT, K, n)
     res = _public(np.ascontiguousarray(np.moveaxis(stats, 1, 2)), n_chains, npc)  # arrays (n, K)
@@ -190,14 +177,13 @@ def relative_efficiency(sampler, X, y, likelihood, points=None, offset=None, dra
     Returns ``reff_i`` ``(n_rows,)``, ``reff`` (their mean: the scalar ``loo(..., reff=res["reff"])`` takes),
     ``reff_min``, ``ess_mean_i``, ``n_draws`` (after the split), ``n_chains``, ``n_per_chain`` and ``n_clamped``."""
     idx, n_chains, npc = _chain_draws(sampler, draws_per_chain, MEAN_ONLY)
-    from .pointwise import _Job
-
-    job = _Job(sampler, X, y, likelihood, points, offset, idx)
+    job = ScoringJob(sampler, X, y, likelihood, points, offset, idx)
     S = 2 * n_chains * (npc // 2)
     ess = np.empty(job.n)
 
-    def diag(lib, mem, md, nb, r0):
-        ess[r0:r0 + nb] = _diag_block(lib, mem, md, n_chains, npc, nb, nb, TRANSFORMS["exp_shift"], MEAN_ONLY)[5]
+    def diag(be, blk):
+        ess[blk.r0:blk.r1] = _diag_block(be.lib, be.mem, blk.md, n_chains, npc, blk.nb, blk.nb, TRANSFORMS["exp_shift"],
+                                         MEAN_ONLY)[5]
 
     _, _, clamped = job.run(matrix=True, summary=False, on_block=diag, scratch=NOUT)
     reff_i = np.minimum(ess / S, 1.0)

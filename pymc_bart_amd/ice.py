@@ -13,47 +13,29 @@ methods (:class:`~pymc_bart_amd.trees.PosteriorSampler`, the multi-chain sampler
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from ._device import device_rows
-
-
-def _block_bytes() -> int:
-    """Device bytes the output of one block of columns may take: ``PGB_ICE_BLOCK_BYTES``, default 1 GiB, floor 64 KiB."""
-    return max(1 << 16, int(os.environ.get("PGB_ICE_BLOCK_BYTES", 1 << 30)))
+from ._stored import block_bytes, check_cols, check_picks, check_X, col_blocks
 
 
 def _checked(X, resident: bool, instances, cols, picks, n_draws: int):
     """The arguments of one ``ice_mean`` call, validated on the host before a backend is touched."""
-    if not resident:
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X[:, None]
-        X = np.ascontiguousarray(X)
-    if len(X.shape) != 2 or int(X.shape[0]) < 1 or int(X.shape[1]) < 1:
-        raise ValueError(f"X must be a matrix (n_rows, p), got shape {tuple(X.shape)}")
+    X = check_X(X, resident)
     p = int(X.shape[1])
     inst = np.asarray(instances, dtype=np.float64)
     if inst.ndim == 1:
         inst = inst[None, :]
     if inst.ndim != 2 or inst.shape[0] < 1 or inst.shape[1] != p:
         raise ValueError(f"instances must have shape (n_inst, p = {p}), got {inst.shape}")
-    cols = np.asarray(cols, dtype=np.int64)
-    if cols.ndim != 1 or cols.size < 1:
-        raise ValueError(f"cols must be a non-empty vector of column indices, got shape {cols.shape}")
-    if cols.min() < 0 or cols.max() >= p:
-        raise ValueError(f"cols must index the {p} columns of X")
+    cols = check_cols(cols, p)
     picks = np.asarray(picks, dtype=np.int64)
     if picks.ndim != 3 or picks.shape[:2] != (cols.size, inst.shape[0]):
         raise ValueError(f"picks must have shape (n_cols, n_inst, n_picks) = ({cols.size}, {inst.shape[0]}, n_picks), "
                          f"got {picks.shape}")
-    if picks.shape[2] < 1 or n_draws < 1:
-        raise ValueError("no draws to average: picks must name at least one of the stored draws per curve")
-    if picks.min() < 0 or picks.max() >= n_draws:
-        raise ValueError(f"picks must index the {n_draws} stored draws")
-    return X, np.ascontiguousarray(inst), np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(picks, dtype=np.int32)
+    picks = check_picks(picks, n_draws, "no draws to average: picks must name at least one of the stored draws per curve")
+    return X, np.ascontiguousarray(inst), cols, picks
 
 
 def _on_host(predict, X, inst, cols, picks, K: int) -> np.ndarray:
@@ -92,11 +74,8 @@ def ice_mean(be, pool, table, m: int, K: int, predict, X, instances, cols, picks
     xd = X if resident else mem.from_host(X)
     idev = mem.from_host(inst)
     carr = pool.as_c()
-    per_col = 8 * n_inst * K * n
-    block = max(1, min(n_cols, _block_bytes() // per_col))
     out = np.empty((n_cols, n_inst, K, n))
-    for c0 in range(0, n_cols, block):
-        c1 = min(n_cols, c0 + block)
+    for c0, c1 in col_blocks(n_cols, 8 * n_inst * K * n, block_bytes("PGB_ICE_BLOCK_BYTES", 1 << 16)):
         cb, pb = np.ascontiguousarray(cols[c0:c1]), np.ascontiguousarray(picks[c0:c1])
         od = mem.empty(((c1 - c0) * n_inst * K * n,), np.float64)
         rc = call(C.byref(carr), fidx.ctypes.data, n_draws, int(m), mem.ptr(xd), n, p, p, mem.ptr(idev), n_inst, p,

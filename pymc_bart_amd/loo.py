@@ -27,7 +27,8 @@ import warnings
 import numpy as np
 
 from . import _abi
-from .pointwise import _Job, _block_bytes
+from ._stored import check_seed, fill_lik, hip_only, matrix_blocks
+from .pointwise import ScoringJob
 
 MAX_DRAWS = 16384  # PGB_PSIS_MAX_DRAWS (include/pgbart_psis.h)
 MAX_TAIL = 448     # PGB_PSIS_MAX_TAIL
@@ -54,15 +55,6 @@ def tail_length(D: int, reff: float = 1.0) -> int:
 
 def khat_threshold(D: int) -> float:
     return min(1.0 - 1.0 / math.log10(D), 0.7)
-
-
-def _hip(backend):
-    from .sampler import default_backend
-
-    be = backend if backend is not None else default_backend()
-    if be.lib.backend_name != "hip-gfx950":
-        raise _abi.PGBError(f"PSIS-LOO runs on the HIP backend only, not on {be.lib.backend_name}")
-    return be
 
 
 def _psis_block(lib, mem, md, D: int, nb: int, ld: int, M: int) -> np.ndarray:
@@ -105,14 +97,10 @@ def psis_loo_matrix(ll, reff: float = 1.0, backend=None) -> dict:
     n_clamped = int(np.sum((ll <= -CLAMP) | (ll >= CLAMP)))
     if n_clamped:
         ll = np.clip(ll, -CLAMP, CLAMP)
-    be = _hip(backend)
-    lib, mem = be.lib, be.mem
-    block = max(64, min(n, _block_bytes() // (8 * (D + 2)) // 64 * 64))
+    be = hip_only(backend, "PSIS-LOO runs")
     out = np.empty((2, n))
-    for r0 in range(0, n, block):
-        r1 = min(n, r0 + block)
-        md = mem.from_host(np.ascontiguousarray(ll[:, r0:r1]))
-        out[:, r0:r1] = _psis_block(lib, mem, md, D, r1 - r0, r1 - r0, M)
+    for r0, r1, md in matrix_blocks(be, 8 * (D + 2), ll):
+        out[:, r0:r1] = _psis_block(be.lib, be.mem, md, D, r1 - r0, r1 - r0, M)
     return _result(out[0].copy(), out[1].copy(), D, M, n_clamped)
 
 
@@ -125,12 +113,12 @@ def loo(sampler, X, y, likelihood, points=None, offset=None, draws=None, reff: f
     ``khat_threshold = min(1 - 1 / log10(D), 0.7)``, ``n_high_k`` (the rows above it: a ``UserWarning`` names them),
     ``tail_len``, ``n_draws`` and ``n_clamped``.  ``pareto_k_i`` is ``inf`` where the tail was too short or too
     degenerate for a fit (then the row's weights are not smoothed)."""
-    job = _Job(sampler, X, y, likelihood, points, offset, draws)
+    job = ScoringJob(sampler, X, y, likelihood, points, offset, draws)
     M = tail_length(job.D, reff)
     out = np.empty((2, job.n))
 
-    def smooth(lib, mem, md, nb, r0):
-        out[:, r0:r0 + nb] = _psis_block(lib, mem, md, job.D, nb, nb, M)
+    def smooth(be, blk):
+        out[:, blk.r0:blk.r1] = _psis_block(be.lib, be.mem, blk.md, job.D, blk.nb, blk.nb, M)
 
     _, stats, clamped = job.run(matrix=True, summary=True, on_block=smooth)
     return _result(out[0].copy(), out[1].copy(), job.D, M, clamped, lppd_i=stats[0].copy())
@@ -185,17 +173,10 @@ def psis_expectation_matrix(ll, g, y=None, kind: str = "value", reff: float = 1.
     n_clamped = int(np.sum((ll <= -CLAMP) | (ll >= CLAMP)))
     if n_clamped:
         ll = np.clip(ll, -CLAMP, CLAMP)
-    be = _hip(backend)
-    lib, mem = be.lib, be.mem
-    block = max(64, min(n, _block_bytes() // (8 * (2 * D + 5)) // 64 * 64))
-    rows = 2 + (2 if kind == "value" else 1)
-    out = np.empty((rows, n))
-    for r0 in range(0, n, block):
-        r1 = min(n, r0 + block)
-        md = mem.from_host(np.ascontiguousarray(ll[:, r0:r1]))
-        gd = mem.from_host(np.ascontiguousarray(g[:, r0:r1]))
-        yd = None if yy is None else mem.from_host(np.ascontiguousarray(yy[r0:r1]))
-        out[:, r0:r1] = _expect_block(lib, mem, md, D, r1 - r0, r1 - r0, M, mem.ptr(gd), r1 - r0, yd, KINDS[kind])
+    be = hip_only(backend, "PSIS-LOO runs")
+    out = np.empty((2 + (2 if kind == "value" else 1), n))
+    for r0, r1, md, gd, yd in matrix_blocks(be, 8 * (2 * D + 5), ll, g, yy):
+        out[:, r0:r1] = _expect_block(be.lib, be.mem, md, D, r1 - r0, r1 - r0, M, be.mem.ptr(gd), r1 - r0, yd, KINDS[kind])
     res = _result(out[0].copy(), out[1].copy(), D, M, n_clamped)
     if kind == "pit":
         res["loo_pit"] = out[2].copy()
@@ -208,16 +189,14 @@ def psis_expectation_matrix(ll, g, y=None, kind: str = "value", reff: float = 1.
 def _expect_job(sampler, X, y, likelihood, points, offset, draws, reff, random_seed, mode: str):
     """The validated job of :func:`loo_pit` / :func:`loo_predictive` -- everything checked on the host before a
     backend is touched -> (job, tail length, seed)."""
-    from .predictive import _check_domain, _check_family
+    from .predictive import check_domain, check_family
 
-    family = _check_family(likelihood) if mode != "mu" else None   # (no sampler: refused by name)
-    job = _Job(sampler, X, y, likelihood, points, offset, draws)
+    family = check_family(likelihood) if mode != "mu" else None   # (no sampler: refused by name)
+    job = ScoringJob(sampler, X, y, likelihood, points, offset, draws)
     M = tail_length(job.D, reff)
-    seed = int(random_seed)
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"random_seed must be an integer in [0, 2^64), got {random_seed!r}")
+    seed = check_seed(random_seed)
     if family is not None:
-        _check_domain(family, job.params)
+        check_domain(family, job.params)
     return job, M, seed
 
 
@@ -225,33 +204,24 @@ def _run_expect(job, M: int, seed: int, mode: str):
     """Per block of rows, with the block's pointwise matrix in device scratch: ``pgb_predict`` -> (``pgb_ppc_draw``, in
     place for K = 1 | ``pgb_add_offset``) -> ``pgb_psis_expect``.  ``mode``: "pit" (y_rep against y), "y" (y_rep),
     "mu" (the linear predictor, one call per output).  -> (psis (2, n), E (calls, n_e, n), row stats, n_clamped, info)."""
-    D, K, n, p = job.D, job.K, job.n, int(job.X.shape[1])
+    D, K, n = job.D, job.K, job.n
     n_e = 1 if mode == "pit" else 2
     kind = KINDS["pit" if mode == "pit" else "value"]
     psis = np.empty((2, n))
     E = np.empty((K if mode == "mu" else 1, n_e, n))
     info = {"n_capped": 0, "n_exhausted": 0}
     flags = (C.c_int64 * 2)()
-    lik = None
-    if mode != "mu":
-        lik = _abi.PpcLik()
-        lik.family = _abi.FAMILIES[job.family]
-        lik.n_params = job.n_par
-        lik.params_host = job.params.ctypes.data if job.n_par else None
-    carr = job.pool.as_c()
+    lik = fill_lik(_abi.PpcLik(), job) if mode != "mu" else None
 
-    def expect(lib, mem, md, nb, r0):
-        xd, yd, od = job.block
-        gd = mem.empty((D * K * nb,), np.float64)  # [D][K][nb]
-        rc = lib.lib.pgb_predict(C.byref(carr), job.fidx.ctypes.data, D, job.m, mem.ptr(xd), nb, p, p, None, 0, mem.ptr(gd),
-                                 mem.stream_ptr)
-        lib.check(rc, "pgb_predict")
+    def expect(be, blk):
+        lib, mem, md, od, nb, r0, r1 = be.lib, be.mem, blk.md, blk.od, blk.nb, blk.r0, blk.r1
+        gd = job.predict(be, blk.xd, nb)  # [D][K][nb]
         if mode == "mu":
             if od is not None:
                 lib.check(lib.add_offset_entry_point()(mem.ptr(gd), D, K, nb, mem.ptr(od), mem.stream_ptr), "pgb_add_offset")
             for k in range(K):
                 o = _expect_block(lib, mem, md, D, nb, nb, M, mem.ptr(gd) + 8 * k * nb, K * nb, None, kind)
-                E[k, :, r0:r0 + nb] = o[2:]
+                E[k, :, r0:r1] = o[2:]
         else:
             lik.offset_dev = None if od is None else mem.ptr(od)
             rd = gd if K == 1 else mem.empty((D * nb,), np.float64)  # (K = 1: in place)
@@ -260,9 +230,9 @@ def _run_expect(job, M: int, seed: int, mode: str):
             lib.check(rc, "pgb_ppc_draw")
             info["n_capped"] += int(flags[0])
             info["n_exhausted"] += int(flags[1])
-            o = _expect_block(lib, mem, md, D, nb, nb, M, mem.ptr(rd), nb, yd if mode == "pit" else None, kind)
-            E[0, :, r0:r0 + nb] = o[2:]
-        psis[:, r0:r0 + nb] = o[:2]
+            o = _expect_block(lib, mem, md, D, nb, nb, M, mem.ptr(rd), nb, blk.yd if mode == "pit" else None, kind)
+            E[0, :, r0:r1] = o[2:]
+        psis[:, r0:r1] = o[:2]
 
     scratch = 2 + n_e + K * D + (D if K > 1 and mode != "mu" else 0)
     _, stats, clamped = job.run(matrix=True, summary=True, on_block=expect, scratch=scratch)

@@ -57,17 +57,17 @@ def _summarised(g, grid, cols, picks, spec, keep_pd: bool):
     """The sweep of one sampler with ``summary=``: ``(pred (n_cols, samples, K, grid) or None, [summary dict per
     column])``.  Every block of the sweep stays on the device: a column's ``[samples][K * rows]`` part of it is the
     matrix ``pgb_row_summary`` takes; only with ``keep_pd`` is the block also copied to the host."""
-    from .pdp import _checked, device_blocks
-    from .shap import _history
-    from .summary import _hip, _result, _spec, _summary_block
+    from ._stored import hip_only, history
+    from .pdp import checked, device_blocks
+    from .summary import result, spec as summary_spec, summary_block
 
-    parts, (pool, table) = _history(g)
-    be = _hip(parts[0]._get_backend())
+    parts, pool, table = history(g)
+    be = hip_only(parts[0]._get_backend(), "posterior summaries run")
     lib, mem = be.lib, be.mem
     K, m = int(parts[0].n_outputs), int(parts[0].m)
     D = int(picks.shape[1])
-    q, hdi_k, code = _spec(D, *spec)
-    X, cols, picks = _checked(grid, False, cols, picks, int(np.asarray(table).shape[0]), 0)
+    q, hdi_k, code = summary_spec(D, *spec)
+    X, cols, picks = checked(grid, False, cols, picks, int(np.asarray(table).shape[0]), 0)
     n = int(X.shape[0])
     stats = np.empty((cols.size, 2 + q.size + 2, K, n))
     pred = np.empty((cols.size, D, K, n)) if keep_pd else None
@@ -75,10 +75,10 @@ def _summarised(g, grid, cols, picks, spec, keep_pd: bool):
         width = K * (r1 - r0)
         for c in range(c0, c1):
             md = od[(c - c0) * D * width:(c - c0 + 1) * D * width]  # [D][K][rows of the block]
-            stats[c, :, :, r0:r1] = _summary_block(lib, mem, md, D, width, width, None, code, q, hdi_k).reshape(-1, K, r1 - r0)
+            stats[c, :, :, r0:r1] = summary_block(lib, mem, md, D, width, width, None, code, q, hdi_k).reshape(-1, K, r1 - r0)
         if keep_pd:
             pred[c0:c1, :, :, r0:r1] = mem.to_host(od).reshape(c1 - c0, D, K, r1 - r0)
-    return pred, [_result(stats[c], n, K, q, spec[1], hdi_k, D) for c in range(cols.size)]
+    return pred, [result(stats[c], n, K, q, spec[1], hdi_k, D) for c in range(cols.size)]
 
 
 def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs_values=None,
@@ -115,7 +115,7 @@ def partial_dependence(bart, X, var_idx=None, xs_interval: str = "quantiles", xs
 
         spec = (summary.get("quantiles", _summary.DEFAULT_QUANTILES), summary.get("hdi_prob", _summary.DEFAULT_HDI_PROB),
                 summary.get("transform", "identity"))
-        _summary._spec(int(samples), *spec)  # (refused before a backend is touched)
+        _summary.spec(int(samples), *spec)  # (refused before a backend is touched)
     elif not keep_pd:
         raise ValueError("keep_pd=False leaves nothing to return without summary=: name the summaries to keep")
     Xm, names = _as_matrix(X)

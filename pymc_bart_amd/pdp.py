@@ -14,45 +14,26 @@ The public call is :func:`pymc_bart_amd.partial.partial_dependence`; the sampler
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from ._device import device_rows
+from ._stored import block_bytes, check_cols, check_picks, check_X, col_blocks, row_blocks
 
 ROUTES = (0, 1, 2)  # PGB_PDP_ROUTE_AUTO, _DIRECT, _PROFILE
 
 
-def _block_bytes() -> int:
-    """Device bytes the output of one block may take: ``PGB_PDP_BLOCK_BYTES``, default 1 GiB, floor 4 KiB."""
-    return max(1 << 12, int(os.environ.get("PGB_PDP_BLOCK_BYTES", 1 << 30)))
-
-
-def _checked(X, resident: bool, cols, picks, n_draws: int, route):
+def checked(X, resident: bool, cols, picks, n_draws: int, route):
     """The arguments of one ``pdp_sweep`` call, validated on the host before a backend is touched."""
-    if not resident:
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X[:, None]
-        X = np.ascontiguousarray(X)
-    if len(X.shape) != 2 or int(X.shape[0]) < 1 or int(X.shape[1]) < 1:
-        raise ValueError(f"X must be a matrix (n_rows, p), got shape {tuple(X.shape)}")
-    p = int(X.shape[1])
-    cols = np.asarray(cols, dtype=np.int64)
-    if cols.ndim != 1 or cols.size < 1:
-        raise ValueError(f"cols must be a non-empty vector of column indices, got shape {cols.shape}")
-    if cols.min() < 0 or cols.max() >= p:
-        raise ValueError(f"cols must index the {p} columns of X")
+    X = check_X(X, resident)
+    cols = check_cols(cols, int(X.shape[1]))
     picks = np.asarray(picks, dtype=np.int64)
     if picks.ndim != 2 or picks.shape[0] != cols.size:
         raise ValueError(f"picks must have shape (n_cols, n_picks) = ({cols.size}, n_picks), got {picks.shape}")
-    if picks.shape[1] < 1 or n_draws < 1:
-        raise ValueError("no draws to predict: picks must name at least one of the stored draws per column")
-    if picks.min() < 0 or picks.max() >= n_draws:
-        raise ValueError(f"picks must index the {n_draws} stored draws")
+    picks = check_picks(picks, n_draws, "no draws to predict: picks must name at least one of the stored draws per column")
     if isinstance(route, bool) or route not in ROUTES:
         raise ValueError(f"route must be 0 (auto), 1 (direct) or 2 (profile where eligible), got {route!r}")
-    return X, np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(picks, dtype=np.int32)
+    return X, cols, picks
 
 
 def _on_host(predict, X, cols, picks) -> np.ndarray:
@@ -67,18 +48,16 @@ def blocks(n_cols: int, n_picks: int, K: int, n: int):
     """The blocks ``(c0, c1, r0, r1)`` of one sweep: whole columns while ``PGB_PDP_BLOCK_BYTES`` holds at least one
     (all rows of each), rows of one column otherwise (multiples of 64)."""
     per_col = 8 * n_picks * K * n
-    limit = _block_bytes()
+    limit = block_bytes("PGB_PDP_BLOCK_BYTES", 1 << 12)
     if per_col <= limit:
-        step = max(1, min(n_cols, limit // per_col))
-        return [(c0, min(n_cols, c0 + step), 0, n) for c0 in range(0, n_cols, step)]
-    rows = max(64, limit // (8 * n_picks * K) // 64 * 64)
-    return [(c, c + 1, r0, min(n, r0 + rows)) for c in range(n_cols) for r0 in range(0, n, rows)]
+        return [(c0, c1, 0, n) for c0, c1 in col_blocks(n_cols, per_col, limit)]
+    return [(c, c + 1, r0, r1) for c in range(n_cols) for r0, r1 in row_blocks(n, 8 * n_picks * K, limit)]
 
 
 def device_blocks(be, pool, table, m: int, K: int, X, cols, picks, route: int = 0, taken=None):
     """Generator over the blocks of a sweep on the HIP backend: ``(c0, c1, r0, r1, buffer)``, ``buffer`` the device
     array ``[c1 - c0][n_picks][K][r1 - r0]`` of that block (valid until the next one is asked for).  The arguments are
-    those :func:`_checked` returns; ``taken``: a list that receives ``(c0, c1, r0, r1, routes of the block's columns)``."""
+    those :func:`checked` returns; ``taken``: a list that receives ``(c0, c1, r0, r1, routes of the block's columns)``."""
     mem, lib = be.mem, be.lib
     call = lib.pdp_entry_point()
     n, p = (int(v) for v in X.shape)
@@ -107,7 +86,7 @@ def pdp_sweep(be, pool, table, m: int, K: int, predict, X, cols, picks, route: i
     mem, lib = be.mem, be.lib
     X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
     n_draws = int(np.asarray(table).shape[0])
-    X, cols, picks = _checked(X, resident, cols, picks, n_draws, route)
+    X, cols, picks = checked(X, resident, cols, picks, n_draws, route)
     if not hasattr(lib.lib, "pgb_predict_pdp"):
         return _on_host(predict, X, cols, picks)
     n = int(X.shape[0])

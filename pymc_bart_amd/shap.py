@@ -16,44 +16,27 @@ only: a backend whose library lacks ``pgb_predict_shap`` (the CPU oracle) raises
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from ._device import device_rows
+from ._stored import block_bytes, check_picks, check_X, hip_only, history, row_blocks
 
 
-def _block_bytes() -> int:
-    """Device bytes the attributions of one block of rows may take: ``PGB_SHAP_BLOCK_BYTES``, default 1 GiB, floor
-    4 KiB."""
-    return max(1 << 12, int(os.environ.get("PGB_SHAP_BLOCK_BYTES", 1 << 30)))
-
-
-def _checked(X, resident: bool, picks, n_draws: int):
+def checked(X, resident: bool, picks, n_draws: int):
     """The arguments of one sweep, validated on the host before a backend is touched."""
-    if not resident:
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X[:, None]
-        X = np.ascontiguousarray(X)
-    if len(X.shape) != 2 or int(X.shape[0]) < 1 or int(X.shape[1]) < 1:
-        raise ValueError(f"X must be a matrix (n_rows, p), got shape {tuple(X.shape)}")
+    X = check_X(X, resident)
     picks = np.asarray(picks, dtype=np.int64)
     if picks.ndim != 1:
         raise ValueError(f"picks must be a vector of draw indices, got shape {picks.shape}")
-    if picks.size < 1 or n_draws < 1:
-        raise ValueError("no draws to attribute: picks must name at least one of the stored draws")
-    if picks.min() < 0 or picks.max() >= n_draws:
-        raise ValueError(f"picks must index the {n_draws} stored draws")
-    return X, np.ascontiguousarray(picks, dtype=np.int32)
+    return X, check_picks(picks, n_draws, "no draws to attribute: picks must name at least one of the stored draws")
 
 
 def blocks(cells_per_row: int, n: int):
     """The row blocks ``(r0, r1)`` of one sweep of ``n`` rows: multiples of 64 rows whose ``cells_per_row`` doubles
     each (attributions: ``n_picks K p``; interactions: ``n_picks K q q``) stay under ``PGB_SHAP_BLOCK_BYTES`` (at
     least 64 rows)."""
-    rows = max(64, _block_bytes() // (8 * cells_per_row) // 64 * 64)
-    return [(r0, min(n, r0 + rows)) for r0 in range(0, n, rows)]
+    return row_blocks(n, 8 * cells_per_row, block_bytes("PGB_SHAP_BLOCK_BYTES", 1 << 12))
 
 
 def _entry(lib):
@@ -64,7 +47,7 @@ def _entry(lib):
 def device_blocks(be, pool, table, m: int, K: int, X, picks):
     """Generator over the row blocks of a sweep on the HIP backend: ``(r0, r1, buffer, base)``, ``buffer`` the device
     array ``[n_picks][K][p][r1 - r0]`` of that block (valid until the next one is asked for), ``base`` ``(n_picks, K)``.
-    The arguments are those :func:`_checked` returns."""
+    The arguments are those :func:`checked` returns."""
     mem, lib = be.mem, be.lib
     call = _entry(lib)
     n, p = (int(v) for v in X.shape)
@@ -87,7 +70,7 @@ def shap_sweep(be, pool, table, m: int, K: int, X, picks):
     ``pgb_predict_shap`` call per block of rows; the result does not depend on the blocking."""
     mem, lib = be.mem, be.lib
     X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
-    X, picks = _checked(X, resident, picks, int(np.asarray(table).shape[0]))
+    X, picks = checked(X, resident, picks, int(np.asarray(table).shape[0]))
     _entry(lib)
     n, p = (int(v) for v in X.shape)
     out = np.empty((picks.size, K, n, p))
@@ -98,17 +81,7 @@ def shap_sweep(be, pool, table, m: int, K: int, X, picks):
     return out, base
 
 
-def _history(sampler):
-    """-> (the chains of the sampler, their pooled ``(pool, table)``)."""
-    from .pointwise import _chains
-    from .trees import pooled_history
-
-    parts = _chains(sampler)
-    cached = getattr(sampler, "pooled_history", None)  # (the multi-chain sampler keeps it)
-    return parts, (cached() if cached is not None else pooled_history(parts))
-
-
-def _picks(n_draws: int, draws, samples, random_seed) -> np.ndarray:
+def chosen_draws(n_draws: int, draws, samples, random_seed) -> np.ndarray:
     if draws is not None and samples is not None:
         raise ValueError("give draws= (indices of stored draws) or samples= (how many to draw at random), not both")
     if draws is not None:
@@ -132,9 +105,9 @@ def shap_values(sampler, X, draws=None, samples=None, random_seed=None) -> dict:
 
     Returns ``{"values": (D, K, n_rows, p), "base": (D, K), "draws": the indices}``; the ``K`` axis is dropped when the
     sampler has one output."""
-    parts, (pool, table) = _history(sampler)
+    parts, pool, table = history(sampler)
     n_draws = int(np.asarray(table).shape[0])
-    picks = _picks(n_draws, draws, samples, random_seed)
+    picks = chosen_draws(n_draws, draws, samples, random_seed)
     K, m = int(parts[0].n_outputs), int(parts[0].m)
     values, base = shap_sweep(parts[0]._get_backend(), pool, table, m, K, X, picks)
     if K == 1:
@@ -142,7 +115,7 @@ def shap_values(sampler, X, draws=None, samples=None, random_seed=None) -> dict:
     return {"values": values, "base": base, "draws": np.asarray(picks, dtype=np.int64).copy()}
 
 
-def _summary_result(by, Q: int, hdi_k, base, K: int, strength_key: str, extra: dict) -> dict:
+def summary_result(by, Q: int, hdi_k, base, K: int, strength_key: str, extra: dict) -> dict:
     """The dict a summary returns, from ``by`` -- the rows of ``pgb_row_summary`` (mean, variance, ``Q`` quantiles,
     HDI) over ``(K, n_rows, ...)`` -- and the draws' ``base``: ``strength_key`` names the mean over the rows of
     ``|mean|``, the ``K`` axis is dropped when the sampler has one output, ``extra`` is added as it is."""
@@ -170,17 +143,17 @@ def shap_summary(sampler, X, draws=None, samples=None, random_seed=None, quantil
     p)`` (``None`` without ``hdi_prob``), ``importance`` ``(K, p)`` -- the mean over the rows of ``|mean|`` --,
     ``base_mean`` ``(K,)``, and ``q``, ``hdi_prob``, ``n_draws``, ``draws``; the ``K`` axis is dropped when the sampler
     has one output.  Blocks stay under ``PGB_SHAP_BLOCK_BYTES``; the result does not depend on it."""
-    from .summary import _hip, _spec, _summary_block
+    from .summary import spec, summary_block
 
-    parts, (pool, table) = _history(sampler)
+    parts, pool, table = history(sampler)
     n_draws = int(np.asarray(table).shape[0])
-    picks = _picks(n_draws, draws, samples, random_seed)
+    picks = chosen_draws(n_draws, draws, samples, random_seed)
     K, m = int(parts[0].n_outputs), int(parts[0].m)
-    q, hdi_k, code = _spec(int(np.asarray(picks).size), quantiles, hdi_prob, "identity")
-    X, picks = _checked(X, False, picks, n_draws)
+    q, hdi_k, code = spec(int(np.asarray(picks).size), quantiles, hdi_prob, "identity")
+    X, picks = checked(X, False, picks, n_draws)
     be = parts[0]._get_backend()
     _entry(be.lib)
-    be = _hip(be)
+    be = hip_only(be, "posterior summaries run")
     lib, mem = be.lib, be.mem
     n, p = (int(v) for v in X.shape)
     D, Q = int(picks.size), int(q.size)
@@ -188,9 +161,9 @@ def shap_summary(sampler, X, draws=None, samples=None, random_seed=None, quantil
     base = None
     for r0, r1, od, b in device_blocks(be, pool, table, m, K, X, picks):
         width = K * p * (r1 - r0)
-        stats[:, :, :, r0:r1] = _summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, p, r1 - r0)
+        stats[:, :, :, r0:r1] = summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, p, r1 - r0)
         base = b.copy()
     by = np.ascontiguousarray(np.swapaxes(stats, 2, 3))  # (rows of the summary, K, n, p)
-    return _summary_result(by, Q, hdi_k, base, K, "importance",
+    return summary_result(by, Q, hdi_k, base, K, "importance",
                            {"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
                             "draws": np.asarray(picks, dtype=np.int64).copy()})

@@ -20,7 +20,8 @@ import ctypes as C
 import numpy as np
 
 from ._device import device_rows
-from .shap import _checked, _history, _picks, _summary_result, blocks
+from ._stored import hip_only, history
+from .shap import blocks, checked, chosen_draws, summary_result
 
 
 def _checked_cols(cols, p: int) -> np.ndarray:
@@ -51,7 +52,7 @@ def _entry(lib):
 def device_blocks(be, pool, table, m: int, K: int, X, cols, picks):
     """Generator over the row blocks of a sweep on the HIP backend: ``(r0, r1, buffer, base)``, ``buffer`` the device
     array ``[n_picks][K][q][q][r1 - r0]`` of that block (valid until the next one is asked for), ``base`` ``(n_picks,
-    K)``.  The arguments are those :func:`_checked` and :func:`_checked_cols` return."""
+    K)``.  The arguments are those :func:`~pymc_bart_amd.shap.checked` and :func:`_checked_cols` return."""
     mem, lib = be.mem, be.lib
     call = _entry(lib)
     n, p = (int(v) for v in X.shape)
@@ -75,7 +76,7 @@ def shap_interaction_sweep(be, pool, table, m: int, K: int, X, picks, cols=None)
     depend on the blocking."""
     mem, lib = be.mem, be.lib
     X, resident = device_rows(mem, X)  # (a device tensor: dense and row-major from here on)
-    X, picks = _checked(X, resident, picks, int(np.asarray(table).shape[0]))
+    X, picks = checked(X, resident, picks, int(np.asarray(table).shape[0]))
     n, p = (int(v) for v in X.shape)
     cols = _checked_cols(cols, p)
     _entry(lib)
@@ -97,9 +98,9 @@ def shap_interaction_values(sampler, X, cols=None, draws=None, samples=None, ran
 
     Returns ``{"values": (D, K, n_rows, q, q), "base": (D, K), "draws": the indices, "cols": the columns}``; the ``K``
     axis is dropped when the sampler has one output."""
-    parts, (pool, table) = _history(sampler)
+    parts, pool, table = history(sampler)
     n_draws = int(np.asarray(table).shape[0])
-    picks = _picks(n_draws, draws, samples, random_seed)
+    picks = chosen_draws(n_draws, draws, samples, random_seed)
     K, m = int(parts[0].n_outputs), int(parts[0].m)
     values, base, cols = shap_interaction_sweep(parts[0]._get_backend(), pool, table, m, K, X, picks, cols)
     if K == 1:
@@ -119,28 +120,28 @@ def shap_interaction_summary(sampler, X, cols=None, draws=None, samples=None, ra
     n_rows, q, q)`` (``None`` without ``hdi_prob``), ``strength`` ``(K, q, q)`` -- the mean over the rows of ``|mean|``
     --, ``base_mean`` ``(K,)``, and ``q``, ``hdi_prob``, ``n_draws``, ``draws``, ``cols``; the ``K`` axis is dropped when
     the sampler has one output.  Blocks stay under ``PGB_SHAP_BLOCK_BYTES``; the result does not depend on it."""
-    from .summary import _hip, _spec, _summary_block
+    from .summary import spec, summary_block
 
-    parts, (pool, table) = _history(sampler)
+    parts, pool, table = history(sampler)
     n_draws = int(np.asarray(table).shape[0])
-    picks = _picks(n_draws, draws, samples, random_seed)
+    picks = chosen_draws(n_draws, draws, samples, random_seed)
     K, m = int(parts[0].n_outputs), int(parts[0].m)
-    q, hdi_k, code = _spec(int(np.asarray(picks).size), quantiles, hdi_prob, "identity")
-    X, picks = _checked(X, False, picks, n_draws)
+    q, hdi_k, code = spec(int(np.asarray(picks).size), quantiles, hdi_prob, "identity")
+    X, picks = checked(X, False, picks, n_draws)
     n, p = (int(v) for v in X.shape)
     cols = _checked_cols(cols, p)
     be = parts[0]._get_backend()
     _entry(be.lib)
-    be = _hip(be)
+    be = hip_only(be, "posterior summaries run")
     lib, mem = be.lib, be.mem
     D, Q, nq = int(picks.size), int(q.size), int(cols.size)
     stats = np.empty((2 + Q + 2, K, nq, nq, n))
     base = None
     for r0, r1, od, b in device_blocks(be, pool, table, m, K, X, cols, picks):
         width = K * nq * nq * (r1 - r0)
-        stats[..., r0:r1] = _summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, nq, nq, r1 - r0)
+        stats[..., r0:r1] = summary_block(lib, mem, od, D, width, width, None, code, q, hdi_k).reshape(-1, K, nq, nq, r1 - r0)
         base = b.copy()
     by = np.ascontiguousarray(np.moveaxis(stats, 4, 2))  # (rows of the summary, K, n, q, q)
-    return _summary_result(by, Q, hdi_k, base, K, "strength",
+    return summary_result(by, Q, hdi_k, base, K, "strength",
                            {"q": q.copy(), "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": D,
                             "draws": np.asarray(picks, dtype=np.int64).copy(), "cols": cols.astype(np.int64)})

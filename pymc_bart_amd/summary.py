@@ -14,13 +14,11 @@ HIP backend only.  Between 2 and :data:`MAX_DRAWS` draws, at most :data:`MAX_QUA
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 
-from . import _abi
-from .pointwise import MAX_OFFSET, _block_bytes, _chains
+from ._stored import Job, drop_k_axis, hip_only, matrix_blocks
 
 MAX_DRAWS = 16384    # PGB_ROWSUM_MAX_DRAWS (include/pgbart_rowsummary.h)
 MAX_QUANTILES = 16   # PGB_ROWSUM_MAX_Q
@@ -40,7 +38,7 @@ def hdi_length(D: int, prob) -> int:
     return max(int(math.floor(prob * int(D))), 1)
 
 
-def _spec(D: int, quantiles, hdi_prob, transform):
+def spec(D: int, quantiles, hdi_prob, transform):
     """-> (q array, hdi_k, transform code) of one call, checked."""
     if transform not in TRANSFORMS:
         raise ValueError(f"unknown transform {transform!r}: use one of {', '.join(TRANSFORMS)}")
@@ -59,16 +57,7 @@ def _spec(D: int, quantiles, hdi_prob, transform):
     return np.ascontiguousarray(q), hdi_length(D, hdi_prob), TRANSFORMS[transform]
 
 
-def _hip(backend):
-    from .sampler import default_backend
-
-    be = backend if backend is not None else default_backend()
-    if be.lib.backend_name != "hip-gfx950":
-        raise _abi.PGBError(f"posterior summaries run on the HIP backend only, not on {be.lib.backend_name}")
-    return be
-
-
-def _summary_block(lib, mem, md, D: int, n_cols: int, ld: int, od, code: int, q: np.ndarray, hdi_k: int) -> np.ndarray:
+def summary_block(lib, mem, md, D: int, n_cols: int, ld: int, od, code: int, q: np.ndarray, hdi_k: int) -> np.ndarray:
     """``(2 + Q + 2, n_cols)`` of the device matrix ``md`` ``[D][ld]`` (``od``: the columns' offsets on the device)."""
     rows = 2 + q.size + 2
     sd = mem.empty((rows * n_cols,), np.float64)
@@ -78,7 +67,7 @@ def _summary_block(lib, mem, md, D: int, n_cols: int, ld: int, od, code: int, q:
     return mem.to_host(sd).reshape(rows, n_cols)
 
 
-def _result(stats: np.ndarray, n: int, K: int, q: np.ndarray, hdi_prob, hdi_k: int, D: int) -> dict:
+def result(stats: np.ndarray, n: int, K: int, q: np.ndarray, hdi_prob, hdi_k: int, D: int) -> dict:
     """``stats`` ``(2 + Q + 2, K, n)`` -> the public dict (arrays ``(..., n, K)``)."""
     by = np.ascontiguousarray(np.moveaxis(stats.reshape(-1, K, n), 1, 2))  # (rows, n, K)
     Q = q.size
@@ -88,89 +77,42 @@ def _result(stats: np.ndarray, n: int, K: int, q: np.ndarray, hdi_prob, hdi_k: i
             "hdi_prob": None if hdi_prob is None else float(hdi_prob), "n_draws": int(D)}
 
 
-class _Job:
-    """Everything of one :func:`posterior_summary` call, validated on the host before a backend is touched."""
+class SummaryJob(Job):
+    """One :func:`posterior_summary` call: the job base plus the summary spec."""
 
     def __init__(self, sampler, X, draws, quantiles, hdi_prob, transform, offset, excluded):
-        parts = _chains(sampler)
-        self.K = K = int(parts[0].n_outputs)
-        self.m = int(parts[0].m)
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X[:, None]
-        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-            raise ValueError(f"X must be a matrix (n_rows, p), got shape {X.shape}")
-        self.X = np.ascontiguousarray(X)
-        n, p = self.n, self.p = int(X.shape[0]), int(X.shape[1])
-        self.offset = None
-        if offset is not None:
-            off = np.asarray(offset, dtype=np.float64)
-            if off.shape == (n,) and K == 1:
-                off = off[None, :]
-            if off.shape != (K, n):
-                raise ValueError(f"offset must have shape (n_outputs, n_rows) = ({K}, {n}), got {off.shape}")
-            if not np.all(np.isfinite(off)) or np.max(np.abs(off)) > MAX_OFFSET:
-                raise ValueError(f"offset must be finite and within +-{MAX_OFFSET:g}")
-            self.offset = np.ascontiguousarray(off)
-        excl = np.asarray([] if excluded is None else excluded, dtype=np.int64).ravel()
-        if excl.size and (excl.min() < 0 or excl.max() >= p):
-            raise ValueError(f"excluded must index the {p} columns of X")
-        self.excluded = np.ascontiguousarray(excl, dtype=np.int32)
-        starts = np.concatenate([[0], np.cumsum([part.forest_idx.shape[0] for part in parts])]).astype(np.int64)
-        total = int(starts[-1])
-        if draws is None:
-            idx = np.arange(total, dtype=np.int64)
-        else:
-            idx = np.asarray(draws, dtype=np.int64).ravel()
-            if idx.size and (idx.min() < 0 or idx.max() >= total):
-                raise ValueError(f"draws must index the {total} stored draws")
-        self.D = D = int(idx.size)
+        super().__init__(sampler)
+        self.take_X(X)
+        self.take_offset(offset)
+        self.take_excluded(excluded)
+        self.take_draws(draws)
         self.hdi_prob = hdi_prob
-        self.q, self.hdi_k, self.code = _spec(D, quantiles, hdi_prob, transform)
-        from .trees import pooled_history
-
-        cached = getattr(sampler, "pooled_history", None)  # (the multi-chain sampler keeps it)
-        self.pool, table = cached() if cached is not None else pooled_history(parts)
-        self.fidx = np.ascontiguousarray(np.asarray(table)[idx], dtype=np.int32)
-        self.backend = parts[0]._get_backend if hasattr(parts[0], "_get_backend") else None
+        self.q, self.hdi_k, self.code = spec(self.D, quantiles, hdi_prob, transform)
+        self.take_history()
 
     def run(self, keep_matrix: bool = False, on_block=None, out_rows: int = 0):
         """-> (the public dict, the predictions ``(D, K, n)`` or None).  ``keep_matrix``: also copy every block's
-        predictions to the host (partial dependence returns them next to their summary).  ``on_block(lib, mem, md,
-        n_cols, od)``: another second kernel on every block's predictions ``md`` ``[D][n_cols]`` in place of
-        ``pgb_row_summary`` (:mod:`pymc_bart_amd.diagnostics`); it returns ``(out_rows, n_cols)`` and the first result
-        is then the array ``(out_rows, K, n)`` itself."""
-        from .sampler import default_backend
-
-        be = _hip(self.backend() if self.backend is not None else default_backend())
-        lib, mem = be.lib, be.mem
+        predictions to the host (partial dependence returns them next to their summary).  ``on_block(be, blk)``:
+        another second kernel on every block's predictions ``blk.md`` ``[D][K * blk.nb]`` in place of
+        ``pgb_row_summary`` (:mod:`pymc_bart_amd.diagnostics`); it returns ``(out_rows, K * blk.nb)`` and the first
+        result is then the array ``(out_rows, K, n)`` itself."""
+        be = self.hip_backend("posterior summaries run")
         n, D, K, p, Q = self.n, self.D, self.K, self.p, self.q.size
         rows = 2 + Q + 2 if on_block is None else int(out_rows)
-        per_row = 8 * (p + K * (D + 1 + rows))
-        block = max(64, min(n, _block_bytes() // per_row // 64 * 64))
         stats = np.empty((rows, K, n))
         pred = np.empty((D, K, n)) if keep_matrix else None
-        carr = self.pool.as_c()
-        excl = self.excluded
-        for r0 in range(0, n, block):
-            r1 = min(n, r0 + block)
-            nb = r1 - r0
-            xd = mem.from_host(self.X[r0:r1])
-            od = None if self.offset is None else mem.from_host(np.ascontiguousarray(self.offset[:, r0:r1]))
-            md = mem.empty((D * K * nb,), np.float64)  # [D][K][nb]: K * nb columns over the draws
-            rc = lib.lib.pgb_predict(C.byref(carr), self.fidx.ctypes.data, D, self.m, mem.ptr(xd), nb, p, p,
-                                     excl.ctypes.data if excl.size else None, int(excl.size), mem.ptr(md), mem.stream_ptr)
-            lib.check(rc, "pgb_predict")
+        for blk in self.blocks(be, 8 * (p + K * (D + 1 + rows)), predict=True):
+            r0, r1, nb = blk.r0, blk.r1, blk.nb
             if on_block is None:
-                blk = _summary_block(lib, mem, md, D, K * nb, K * nb, od, self.code, self.q, self.hdi_k)
+                got = summary_block(be.lib, be.mem, blk.md, D, K * nb, K * nb, blk.od, self.code, self.q, self.hdi_k)
             else:
-                blk = on_block(lib, mem, md, K * nb, od)
-            stats[:, :, r0:r1] = blk.reshape(-1, K, nb)
+                got = on_block(be, blk)
+            stats[:, :, r0:r1] = got.reshape(-1, K, nb)
             if keep_matrix:
-                pred[:, :, r0:r1] = mem.to_host(md).reshape(D, K, nb)
+                pred[:, :, r0:r1] = be.mem.to_host(blk.md).reshape(D, K, nb)
         if on_block is not None:
             return stats, pred
-        return _result(stats, n, K, self.q, self.hdi_prob, self.hdi_k, D), pred
+        return result(stats, n, K, self.q, self.hdi_prob, self.hdi_k, D), pred
 
 
 def posterior_summary(sampler, X, draws=None, quantiles=DEFAULT_QUANTILES, hdi_prob=DEFAULT_HDI_PROB,
@@ -189,7 +131,7 @@ def posterior_summary(sampler, X, draws=None, quantiles=DEFAULT_QUANTILES, hdi_p
     ``(2, n_rows, K)`` (``None`` without ``hdi_prob``); and ``q``, ``hdi_prob``, ``n_draws``.  Rows are processed in
     blocks of at most ``PGB_PW_BLOCK_BYTES`` of device scratch; results do not depend on the blocking, nor on the
     order of the draws."""
-    return _Job(sampler, X, draws, quantiles, hdi_prob, transform, offset, excluded).run()[0]
+    return SummaryJob(sampler, X, draws, quantiles, hdi_prob, transform, offset, excluded).run()[0]
 
 
 def summarize_matrix(a, quantiles=DEFAULT_QUANTILES, hdi_prob=DEFAULT_HDI_PROB, transform: str = "identity",
@@ -200,19 +142,11 @@ def summarize_matrix(a, quantiles=DEFAULT_QUANTILES, hdi_prob=DEFAULT_HDI_PROB, 
     if a.ndim != 2 or a.shape[1] < 1:
         raise ValueError(f"a must be a matrix (draws, columns), got shape {a.shape}")
     D, n = int(a.shape[0]), int(a.shape[1])
-    q, hdi_k, code = _spec(D, quantiles, hdi_prob, transform)
+    q, hdi_k, code = spec(D, quantiles, hdi_prob, transform)
     if not np.all(np.isfinite(a)):
         raise ValueError("a must be finite")
-    be = _hip(backend)
-    lib, mem = be.lib, be.mem
-    block = max(64, min(n, _block_bytes() // (8 * (D + 4 + q.size)) // 64 * 64))
+    be = hip_only(backend, "posterior summaries run")
     stats = np.empty((2 + q.size + 2, n))
-    for r0 in range(0, n, block):
-        r1 = min(n, r0 + block)
-        md = mem.from_host(np.ascontiguousarray(a[:, r0:r1]))
-        stats[:, r0:r1] = _summary_block(lib, mem, md, D, r1 - r0, r1 - r0, None, code, q, hdi_k)
-    res = _result(stats, n, 1, q, hdi_prob, hdi_k, D)
-    for key in ("mean", "sd", "var", "quantiles", "hdi"):
-        if res[key] is not None:
-            res[key] = res[key][..., 0]
-    return res
+    for r0, r1, md in matrix_blocks(be, 8 * (D + 4 + q.size), a):
+        stats[:, r0:r1] = summary_block(be.lib, be.mem, md, D, r1 - r0, r1 - r0, None, code, q, hdi_k)
+    return drop_k_axis(result(stats, n, 1, q, hdi_prob, hdi_k, D))

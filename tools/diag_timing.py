@@ -82,7 +82,7 @@ def _kernel_alone(sampler, X, n_chains, npc, reps):
 
     from pymc_bart_amd import diagnostics, summary
 
-    job = summary._Job(sampler, X, None, None, None, "identity", None, None)
+    job = summary.SummaryJob(sampler, X, None, None, None, "identity", None, None)
     be = job.backend()
     lib, mem = be.lib, be.mem
     n, D, K, p = job.n, job.D, job.K, job.p

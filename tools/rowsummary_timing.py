@@ -111,7 +111,7 @@ def _kernel_alone(sampler, X, reps):
 
     from pymc_bart_amd import summary
 
-    job = summary._Job(sampler, X, None, QUANTILES, HDI_PROB, "identity", None, None)
+    job = summary.SummaryJob(sampler, X, None, QUANTILES, HDI_PROB, "identity", None, None)
     be = job.backend()
     lib, mem = be.lib, be.mem
     n, D, K, p = job.n, job.D, job.K, job.p

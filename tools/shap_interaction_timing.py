@@ -42,7 +42,7 @@ def _kernels_alone(s, X, picks, cols, reps):
     be = part._get_backend()
     pool, table = s.pooled_history()
     K, m = int(part.n_outputs), int(part.m)
-    Xc, pk = shap._checked(X, False, picks, int(np.asarray(table).shape[0]))
+    Xc, pk = shap.checked(X, False, picks, int(np.asarray(table).shape[0]))
     cc = shap_interaction._checked_cols(cols, Xc.shape[1])
     x_ms, s_ms = be.lib.lib.pgb_shap_interactions_kernel_ms, be.lib.lib.pgb_shap_kernel_ms
     x_ms.argtypes = s_ms.argtypes = [C.POINTER(C.c_double)]

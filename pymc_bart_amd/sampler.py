@@ -470,6 +470,10 @@ class PySampler:
         buf = np.frombuffer(blob, np.uint8)
         lib.check(lib.lib.pgb_checkpoint_load(self._h, buf.ctypes.data, buf.size), "pgb_checkpoint_load")
         self._lik_key = None  # the image carries its own likelihood parameters
+        # ... and its own saturation counter: events the chain reported before the image was taken are not news
+        from .image import ImageHeader
+
+        self._sat_seen = int(ImageHeader.from_buffer_copy(blob[: C.sizeof(ImageHeader)]).ctr.saturations)
 
     def profile(self, enable: bool) -> tuple[float, int]:
         lib = self.backend.lib

@@ -5,7 +5,7 @@ import hashlib
 
 import numpy as np
 
-from pymc_bart_amd.sampler import PyBartSettings, PySampler
+from pymc_bart_amd.sampler import PyBartSettings, PySampler, range_exponent
 
 
 def make_case(name: str):
@@ -1007,4 +1007,434 @@ def check_cap_reach(c, res):
     assert not dropped or r["dropped"] > 0, f"{c['name']}: no 255-node tree has dropped rows: {r}"
     assert r["saturations"] == 0, f"{c['name']}: fixed-point saturation: {r}"
     assert r["leaf_sd_tuned"], f"{c['name']}: tuning did not change leaf_sd: {r}"
+    return r
+
+
+# ------------------------------------------------------------------ saturating steps (tests/test_saturation*.py)
+# Every term of the sampler's sums is quantised to fixed point (pgb_quant, include/pgbart_spec.h): a term beyond the
+# declared range 2^range_exp is clamped to +-2^50 and COUNTED in counters.saturations, and PySampler turns a moved
+# counter into an error.  The cases below make that counter move: a response that leaves the range for one step
+# (set_response, as the other terms of an additive model move it), for the whole run, or a range set below the
+# data's.  One tree is re-sampled per step, so a step's events are those of one tree update -- on the device, a row
+# pass that starts a tree (INIT) and a pass of its own that ends it (the lone FINAL).  The two */two_per_step cases
+# re-sample two: the first tree of a step ends in the pass that starts the second (FINAL + INIT in one launch).
+SAT_CASES = ["sat/normal_outliers", "sat/normal_linear", "sat/normal_all_rows_top", "sat/normal_one_tree", "sat/edge_exact",
+             "sat/poisson_small_range", "sat/probit_small_range", "sat/categorical_k3", "sat/categorical_k6",
+             "sat/particles_100", "sat/probit_two_per_step", "sat/categorical_k3_two_per_step"]
+SAT_OUTLIER_CASES = ("sat/normal_outliers", "sat/normal_linear", "sat/particles_100")
+SAT_OUTLIER_ROWS = (0, 3, 255, 256, 512, 1023, 1024)   # chunk edges of 256 and 1024 rows; 1024: the lone row of the second chunk
+SAT_OUTLIER_MULT = (1.5, -2.0, 3.0, -3.0, -1.0001, 2.5, 1.25)   # (-1.0001: back inside once sum_trees_noi is taken off)
+# name -> the first seed whose oracle run meets check_sat_reach, where seed 0 does not
+SAT_SEEDS = {}
+SAT_QLIM = 2.0 ** 50
+
+
+def sat_scales(n, range_exp):
+    """pgb_make_scales (include/pgbart_spec.h): (frac, c1, c2)."""
+    bits = 0
+    while (1 << bits) < n + 1:
+        bits += 1
+    frac = min(61 - bits, 50)
+    return frac, 2.0 ** (frac - range_exp), 2.0 ** (frac - 2 * range_exp)
+
+
+def sat_quant(x, scale):
+    """pgb_quant on arrays: (the integers, the number of terms counted).  NaN -> 0, counted."""
+    t = np.asarray(x, np.float64) * scale
+    nan = np.isnan(t)
+    t = np.where(nan, 0.0, t)
+    over = np.abs(t) > SAT_QLIM
+    q = np.rint(np.clip(t, -SAT_QLIM, SAT_QLIM)).astype(np.int64)   # (rint: to nearest even, exact below 2^51)
+    return q, int(nan.sum() + over.sum())
+
+
+def sat_case(name, seed):
+    rng = np.random.default_rng([SAT_CASES.index(name), int(seed)])
+    c = dict(name=name, m=5, P=10, steps=8, batch=(0.1, 0.1), rules=None, prior=None, seed=4000 + int(seed), range_exp=None,
+             responses={}, sat_steps=(), beta=1.0)
+    if name in SAT_OUTLIER_CASES:
+        # steps 0-2 clean; before step 3 seven rows leave +-2^range_exp, both signs; before step 4 they are back
+        n, p = 1025, 3
+        X = rng.uniform(-2, 2, size=(n, p))
+        Y = np.where(X[:, 0] < 0, 2 * X[:, 0] + 1, -1.5 * X[:, 0] + 1) + rng.normal(0, 0.3, n)
+        out = Y.copy()
+        out[list(SAT_OUTLIER_ROWS)] = np.array(SAT_OUTLIER_MULT) * 2.0 ** range_exponent(Y)
+        c.update(responses={3: out, 4: Y}, sat_steps=(3,), hot_rows=SAT_OUTLIER_ROWS)
+        if name == "sat/normal_linear":
+            c.update(response="linear")
+        elif name == "sat/particles_100":
+            c.update(P=100, m=3)
+    elif name == "sat/normal_all_rows_top":
+        # every row at 64 * 2^range_exp, then at 2 * 2^range_exp, then the data: n = 2049 has frac = 49, so a term
+        # x c1 saturates beyond 2 * 2^range_exp and a squared term beyond sqrt(2) * 2^range_exp.  The sums B, C and E0
+        # of the first update are n * 2^50.  sum_trees itself stays in range -- leaf values are drawn from the clamped
+        # sums -- so A is not among them (sat/categorical_k*: A and Ax at n * 2^50 in the first update)
+        n, p = 2049, 2
+        X = rng.normal(size=(n, p))
+        Y = X[:, 0] + rng.normal(0, 0.3, n)
+        top = 2.0 ** range_exponent(Y)
+        c.update(m=3, steps=8, responses={0: np.full(n, 64.0 * top), 1: np.full(n, 2.0 * top), 2: Y}, sat_steps=(0, 1))
+    elif name == "sat/normal_one_tree":
+        # a few rows out of range for the whole run, no tuning: every term counted is one of A, B, C, E0 of the
+        # row pass that starts a tree, which NumPy recounts from the returned sum_trees and the exported trees
+        n, p = 257, 2
+        X = rng.normal(size=(n, p))
+        clean = np.sin(2 * X[:, 0]) + rng.normal(0, 0.2, n)
+        Y = clean.copy()
+        Y[[0, 100, 255, 256]] = np.array([1.5, -1.004, 1.002, -1.01]) * 2.0 ** 4   # (three of them within reach of a leaf value)
+        c.update(m=4, batch=(1, 1), steps=12, tune_steps=0, range_exp=4, bart_Y=clean, sat_steps="all",
+                 hot_rows=(0, 100, 255, 256))
+    elif name == "sat/edge_exact":
+        # responses exactly +-2^range_exp are not counted (the compare is strict), their neighbours beyond are.  The
+        # settings are sized on a response of dyadic values in +- pairs: init_leaf is exactly 0, so with one tree
+        # r = y exactly at every update
+        n, p, e = 130, 2, 4
+        X = rng.normal(size=(n, p))
+        half = np.round(rng.normal(0, 1, n // 2) * 64) / 64
+        clean = np.concatenate([half, -half])
+        Y = clean.copy()
+        top = 2.0 ** e
+        edge = {0: top, 1: -top, 2: np.nextafter(top, np.inf), 3: np.nextafter(-top, -np.inf), 64: np.nextafter(top, 0.0),
+                129: np.nextafter(-top, 0.0)}
+        for i, v in edge.items():
+            Y[i] = v
+        clean[sorted(set(edge) | {(i + n // 2) % n for i in edge})] = 0.0   # (the edge rows and their partners: the mean stays exactly 0)
+        c.update(m=1, batch=(1, 1), steps=4, range_exp=e, bart_Y=clean, sat_steps="all", hot_rows=(2, 3), edge=edge)
+    elif name == "sat/poisson_small_range":
+        n, p = 1025, 3
+        X = rng.normal(size=(n, p))
+        Y = rng.poisson(np.exp(np.clip(1 + 1.5 * X[:, 0], -3, 6))).astype(float)
+        c.update(family="poisson_log", bart_Y=np.log(Y + 0.5), range_exp=1, sat_steps=tuple(range(1, 8)))   # (step 0: sum_trees is init_sum < 2)
+    elif name == "sat/probit_small_range":
+        # range 2^0 with leaf_sd = 1.5: the running sd of a tree's predictions (tuning) leaves it next to sum_trees
+        from scipy.special import ndtr
+        n, p = 255, 3
+        X = rng.normal(size=(n, p))
+        Y = (rng.random(n) < ndtr(1.5 * X[:, 0])).astype(float)
+        c.update(family="bernoulli_probit", range_exp=0, sat_steps=tuple(range(1, 10)), steps=10, tune_steps=8, m=4, batch=(1, 1))
+    elif name == "sat/probit_two_per_step":
+        # range 2^-2, below most of what moves: a tuning step of two tree updates counts sum_trees twice, the running sd
+        # in the pass that starts the second tree and in the lone FINAL -- more events than three of those can give
+        from scipy.special import ndtr
+        n, p = 255, 3
+        X = rng.normal(size=(n, p))
+        Y = (rng.random(n) < ndtr(1.5 * X[:, 0])).astype(float)
+        c.update(family="bernoulli_probit", range_exp=-2, sat_steps="all", steps=6, tune_steps=4, m=4, batch=(2, 2))
+    elif name == "sat/categorical_k3_two_per_step":
+        n, p, K = 257, 3, 3
+        X = rng.normal(size=(n, p))
+        logits = np.stack([1.5 * X[:, 0] * (k - 0.5 * (K - 1)) for k in range(K)]) + rng.gumbel(size=(K, n))
+        Y = np.argmax(logits, axis=0).astype(float)
+        c.update(family="categorical", K=K, range_exp=-4, sat_steps="all", steps=6, tune_steps=4, m=4, batch=(2, 2))
+    elif name in ("sat/categorical_k3", "sat/categorical_k6"):
+        K = int(name[-1])
+        n, p = (1025, 3) if K == 3 else (257, 3)
+        X = rng.normal(size=(n, p))
+        logits = np.stack([1.5 * X[:, 0] * (k - 0.5 * (K - 1)) for k in range(K)]) + rng.gumbel(size=(K, n))
+        Y = np.argmax(logits, axis=0).astype(float)
+        c.update(family="categorical", K=K, range_exp=-1, sat_steps="all", m=4, batch=(1, 1))
+    else:
+        raise KeyError(name)
+    c.update(X=X, Y=Y)
+    return c
+
+
+def make_sat(name):
+    return sat_case(name, SAT_SEEDS.get(name, 0))
+
+
+def sat_settings(c):
+    X = c["X"]
+    return PyBartSettings.from_data(X, c.get("bart_Y", c["Y"]), m=c["m"], num_particles=c["P"], seed=c["seed"], batch=c["batch"],
+                                    alpha=c.get("alpha", 0.95), beta=c.get("beta", 2.0), family=c.get("family", "normal"),
+                                    n_outputs=c.get("K", 1), response=c.get("response", "constant"),
+                                    compat=c.get("compat", 0), range_exp=c.get("range_exp"))
+
+
+def step_keeping_outputs(s, tune, how="host"):
+    """One astep as PySampler runs it, keeping the outputs of a step whose saturation check raises:
+    (sum_trees, vi, the PGBError or None).  `how`: "host" -- pgb_step_host and PySampler's own check, as `step(tune)`;
+    "device" -- `step(tune, fetch=False)`, sum_trees read from the device buffer; "async" -- `step_async(tune, 1)` and
+    `sync()`, sum_trees read from the chain image."""
+    import ctypes as C
+
+    from pymc_bart_amd import _abi
+
+    lib, mem = s.backend.lib, s.backend.mem
+    K, n = s.settings.n_outputs, s.settings.n
+    err = None
+    if how == "host":
+        st = mem.host_result(K * n)
+        s._steps += 1
+        s._check(lib.lib.pgb_step_host(s._h, int(bool(tune)), st.ctypes.data, s._vi.ctypes.data, C.byref(s.counters)),
+                 "pgb_step_host")
+        try:
+            s._check_saturation()
+        except _abi.PGBError as e:
+            err = e
+    else:
+        try:
+            if how == "device":
+                s.step(tune, fetch=False)
+            else:
+                assert how == "async", how
+                s.step_async(tune, 1)
+                s.sync()
+        except _abi.PGBError as e:
+            if "saturation events" not in str(e):
+                raise
+            err = e
+        if how == "device":
+            st = np.asarray(mem.to_host(s.sum_trees_device()), np.float64).ravel()[: K * n].copy()
+        else:
+            from pymc_bart_amd.image import ChainImage
+
+            st = np.array(ChainImage.parse(s.checkpoint()).sum_trees, np.float64).ravel()
+    return (st.reshape(K, n) if K > 1 else st), s._vi.copy(), err
+
+
+def run_sat_case(c, backend, checkpoint_at=(), setup=None, how="host"):
+    """run_case for a saturating case: the same loop, driven by the case's schedule of responses (`responses`:
+    {step: y}, handed to set_response before that step), through steps that raise.  Next to everything run_case
+    returns: per step `sat` (counters.saturations after it), `raised` (whether the step raised the saturation error)
+    and `raised_count` (the count in its text, or -1); `exports`, the decoded trees of every step.
+    `checkpoint_at` as in run_case (the fresh sampler is built on the response in force)."""
+    import re
+
+    X, y = c["X"], c["Y"]
+    p = X.shape[1]
+    family = c.get("family", "normal")
+    st = sat_settings(c)
+    rules = np.zeros(p, np.int32) if c["rules"] is None else c["rules"]
+    prior = np.ones(p) if c["prior"] is None else c["prior"]
+    s = PySampler(st, X, y, rules, prior, backend=backend)
+    if setup is not None:
+        setup(s)
+    weights0 = s.split_weights()
+    sig_rng = np.random.default_rng(99)
+    sums, vis, trees, split_vars, sat, raised, raised_count, exports = [], [], [], [], [], [], [], []
+    half = c.get("tune_steps", c["steps"] // 2)
+    for it in range(c["steps"]):
+        if it in checkpoint_at:
+            blob = s.checkpoint()
+            del s
+            if isinstance(checkpoint_at, dict):
+                backend = checkpoint_at[it]
+            s = PySampler(st, X, y, rules, prior, backend=backend)
+            if setup is not None:
+                setup(s)
+            s.restore(blob)
+        if it in c["responses"]:
+            y = c["responses"][it]
+            s.set_response(y)
+        sig = float(0.5 + sig_rng.random())
+        s.set_likelihood([sig] if family == "normal" else c.get("lik_params", []))
+        stv, vi, err = step_keeping_outputs(s, it < half, how)
+        sums.append(stv)
+        vis.append(vi)
+        sat.append(int(s.counters.saturations))
+        raised.append(err is not None)
+        mt = re.match(r"(\d+) fixed-point saturation events by astep \d+:", str(err)) if err is not None else None
+        assert err is None or mt is not None, str(err)
+        raised_count.append(int(mt.group(1)) if mt else -1)
+        ta = s.export_trees(0)
+        parts = [ta.tree_id, ta.node_off, ta.var, ta.left, ta.right, ta.count, ta.split.view(np.int64),
+                 ta.value.ravel().view(np.int64)]
+        if c.get("response", "constant") != "constant":
+            parts += [ta.slope.ravel().view(np.int64), ta.xbar.view(np.int64), ta.svar]
+        trees.append(np.concatenate(parts))
+        exports.append(ta.decoded())
+        split_vars.append(np.asarray(ta.var)[np.asarray(ta.var) >= 0].astype(np.int64))
+    forest = s.export_trees(1)
+    ctr = s.counters.as_dict()
+    ctr.pop("slots")
+    return dict(sum_trees=np.array(sums), vi=np.array(vis), trees=trees, forest=forest, counters=ctr,
+                state=s.state(), split_weights=s.split_weights(), sampler=s, split_vars=split_vars,
+                split_weights_init=weights0, sat=sat, raised=raised, raised_count=raised_count, exports=exports,
+                settings=st, response_in_force=y)
+
+
+def sat_digest(res) -> dict:
+    """`digest` plus the per-step saturation counts and raised flags (what tests/golden/sat_runs.json stores)."""
+    d = digest(res)
+    d.update(sat=[int(v) for v in res["sat"]], raised=[bool(v) for v in res["raised"]],
+             raised_count=[int(v) for v in res["raised_count"]])
+    return d
+
+
+def sat_events(res):
+    """Events of every step (one tree update each): the differences of the counter."""
+    return np.diff(np.concatenate([[0], np.asarray(res["sat"], np.int64)]))
+
+
+def sat_response_at(c, it):
+    y = c["Y"]
+    for k in sorted(c["responses"]):
+        if k <= it:
+            y = c["responses"][k]
+    return y
+
+
+def sat_route(ta, t, X):
+    """Leaf (node index in `ta`) of every row of X in tree `t` of an export: continuous rules, no missing values."""
+    base = int(ta.node_off[t])
+    node = np.full(X.shape[0], base, np.int64)
+    for _ in range(256):
+        j = ta.var[node]
+        inner = j >= 0
+        if not inner.any():
+            return node
+        rows = np.flatnonzero(inner)
+        left = X[rows, j[rows]] <= ta.split[node[rows]]
+        node[rows] = base + np.where(left, ta.left[node[rows]], ta.right[node[rows]])
+    raise AssertionError("the walk does not end")
+
+
+def sat_recount_first(c, st):
+    """The terms counted by the first tree update of a Normal case, from include/pgbart_spec.h alone: sum_trees is
+    init_sum and the tree being replaced predicts init_leaf in every row.  Returns (count, sums A, B, C, E0)."""
+    y = sat_response_at(c, 0)
+    n = y.shape[0]
+    _, c1, c2 = sat_scales(n, st.range_exp)
+    stv = np.full(n, st.init_sum)
+    return sat_recount_update(stv, np.full(n, st.init_leaf), y, c1, c2)
+
+
+def sat_recount_update(stv, o, y, c1, c2):
+    """The sums that start a Normal tree update, written from include/pgbart_spec.h alone (pgb_quant, pgb_make_scales,
+    "r = y - sum_trees_noi"): with sum_trees `stv` and the replaced tree's predictions `o`, [U] sum_trees_noi =
+    sum_trees - old_tree.predict(), r = y - noi, and e = r - o is the residual under the current tree; the terms are
+    st c1 (A), r c1 (B), r^2 c2 (C), e^2 c2 (E0).  Returns (terms counted, A, B, C, E0)."""
+    noi = stv - o
+    r = y - noi
+    e = r - o
+    (A, na), (B, nb), (Cq, nc), (E0, ne) = sat_quant(stv, c1), sat_quant(r, c1), sat_quant(r * r, c2), sat_quant(e * e, c2)
+    return na + nb + nc + ne, int(A.sum()), int(B.sum()), int(Cq.sum()), int(E0.sum())
+
+
+def sat_terms_per_row(stv, o, y, c1, c2):
+    """sat_recount_update's count, row by row."""
+    noi = stv - o
+    r = y - noi
+    e = r - o
+    return sum((np.abs(x * k) > SAT_QLIM).astype(np.int64) for x, k in ((stv, c1), (r, c1), (r * r, c2), (e * e, c2)))
+
+
+def sat_outlier_step_per_row(c, res):
+    """Terms counted per row in the saturating step of an outlier case: the tree replaced there is still the initial
+    stump, or (constant leaves) its last export is routed in NumPy."""
+    it = c["sat_steps"][0]
+    st = res["settings"]
+    n = c["X"].shape[0]
+    _, c1, c2 = sat_scales(n, st.range_exp)
+    t = int(res["exports"][it].tree_id[0])
+    before = [j for j in range(it) if int(res["exports"][j].tree_id[0]) == t]
+    if not before:
+        o = np.full(n, st.init_leaf)
+    else:
+        assert c.get("response", "constant") == "constant"
+        old = res["exports"][before[-1]]
+        o = old.value[sat_route(old, 0, c["X"]), 0]
+    return sat_terms_per_row(np.asarray(res["sum_trees"][it - 1]), o, sat_response_at(c, it), c1, c2)
+
+
+def sat_recount_run(c, res):
+    """Events of every step of a Normal case without tuning and with constant leaves, recounted in NumPy from the
+    previous step's returned sum_trees, the previous export of the tree being replaced and the response in force."""
+    assert c.get("family", "normal") == "normal" and c.get("tune_steps", 1) == 0 and c.get("response", "constant") == "constant"
+    st = res["settings"]
+    n, m = c["X"].shape[0], c["m"]
+    _, c1, c2 = sat_scales(n, st.range_exp)
+    last = {}     # tree -> (export, index in it)
+    out = []
+    for it in range(c["steps"]):
+        ta = res["exports"][it]
+        assert ta.n_trees == 1
+        t = int(ta.tree_id[0])
+        stv = np.full(n, st.init_sum) if it == 0 else np.asarray(res["sum_trees"][it - 1])
+        if t in last:
+            old, k = last[t]
+            o = old.value[sat_route(old, k, c["X"]), 0]
+        else:
+            o = np.full(n, st.init_leaf)
+        out.append(sat_recount_update(stv, o, sat_response_at(c, it), c1, c2)[0])
+        last[t] = (ta, 0)
+    return np.array(out, np.int64)
+
+
+def sat_recount_sum_trees(c, res):
+    """Per-row families: the events of every step that come from sum_trees itself (st c1 of every output, counted by
+    the row pass that starts the update), recounted from the previous step's returned sum_trees.  What a tuning step
+    counts beyond them is the running sd of the new tree's predictions; a log-likelihood term cannot saturate."""
+    st = res["settings"]
+    n, K = c["X"].shape[0], c.get("K", 1)
+    _, c1, _ = sat_scales(n, st.range_exp)
+    out = []
+    for it in range(c["steps"]):
+        stv = np.full((K, n), st.init_sum) if it == 0 else np.asarray(res["sum_trees"][it - 1]).reshape(K, n)
+        out.append(sat_quant(stv, c1)[1])
+    return np.array(out, np.int64)
+
+
+def sat_reach(c, res):
+    n = c["X"].shape[0]
+    ev = sat_events(res)
+    half = c.get("tune_steps", c["steps"] // 2)
+    moved = tuple(int(i) for i in np.flatnonzero(ev > 0))
+    r = dict(events=ev.tolist(), moved=moved, n=n,
+             nodes=[int(np.diff(ta.node_off).max()) for ta in res["exports"]], tune_steps=half)
+    if c.get("family", "normal") != "normal":
+        base = sat_recount_sum_trees(c, res)
+        r.update(from_sum_trees=base.tolist(), from_running_sd=(ev - base).tolist())
+    return r
+
+
+def check_sat_reach(c, res):
+    """The conditions a saturating case exists for, evaluated on the oracle's run (no pytest here: the golden generator
+    calls it too)."""
+    r = sat_reach(c, res)
+    name, n, ev = c["name"], r["n"], np.asarray(r["events"])
+    steps = range(c["steps"])
+    named = c["sat_steps"]
+    if named == "all":
+        named = tuple(steps)
+    assert r["moved"] == tuple(named), f"{name}: the counter moved in steps {r['moved']}, the case names {named}: {r}"
+    assert res["raised"] == [it in named for it in steps], f"{name}: raised {res['raised']}"
+    assert [k for k in res["raised_count"] if k >= 0] == [int(ev[it]) for it in named], f"{name}: {res['raised_count']} {r}"
+    if name.endswith("two_per_step"):
+        # a step's events: sum_trees at the start of both updates (the first recounted, the second at most K n), the
+        # running sd at the end of the first (in the pass that starts the second) and of the second (the lone FINAL,
+        # at most K n): what is left over all bounds is a lower bound of the events of the FINAL + INIT pass
+        Kn = c.get("K", 1) * n
+        fused = ev - np.asarray(r["from_sum_trees"]) - 2 * Kn
+        r.update(running_sd_of_first_update_at_least=fused.tolist())
+        assert fused[:r["tune_steps"]].max() > 0, f"{name}: the running sd of a step's first update is not shown to saturate: {r}"
+        assert np.all(ev[r["tune_steps"]:] <= 2 * Kn), f"{name}: {r}"
+        return r
+    if name not in ("sat/normal_all_rows_top", "sat/categorical_k3", "sat/categorical_k6"):
+        assert all(0 < ev[it] < n for it in named), f"{name}: events not strictly between 0 and n = {n}: {r}"
+    assert any(r["nodes"][it] > 1 for it in named), f"{name}: only stumps grown on saturated sums: {r}"
+    if name in SAT_OUTLIER_CASES:   # the lone row of the second chunk is among the rows counted, and only moved rows are
+        per_row = sat_outlier_step_per_row(c, res)
+        assert per_row.sum() == ev[named[0]] and per_row[n - 1] > 0, f"{name}: {per_row[list(c['hot_rows'])]} {r}"
+        assert set(np.flatnonzero(per_row).tolist()) <= set(c["hot_rows"]) and np.count_nonzero(per_row) >= 6, f"{name}: {r}"
+        r.update(terms_of_the_moved_rows=per_row[list(c["hot_rows"])].tolist())
+    if c.get("family", "normal") != "normal":
+        sd = np.asarray(r["from_running_sd"])
+        assert np.all(sd >= 0) and np.all(sd[r["tune_steps"]:] == 0), f"{name}: events beyond sum_trees outside tuning: {r}"
+        assert np.asarray(r["from_sum_trees"]).sum() > 0, f"{name}: sum_trees never saturates: {r}"
+        if name != "sat/poisson_small_range":
+            assert sd.sum() > 0, f"{name}: the running sd never leaves the range: {r}"
+        if c.get("K", 1) > 1:   # outputs 1 .. K-1 are counted on their own (Ax): A and every Ax at n * 2^50 in the first update
+            st = res["settings"]
+            q, cnt = sat_quant(np.full((c["K"], n), st.init_sum), sat_scales(n, st.range_exp)[1])
+            assert cnt == ev[0] == c["K"] * n and np.all(np.abs(q.sum(axis=1)) == n * 2 ** 50), f"{name}: {r}"
+    if name == "sat/normal_all_rows_top":
+        st = res["settings"]
+        frac, c1, c2 = sat_scales(n, st.range_exp)
+        assert frac < 50
+        cnt, A, B, Cq, E0 = sat_recount_first(c, st)
+        assert (B, Cq, E0) == (n * 2 ** 50,) * 3 and cnt == ev[0] == 3 * n, f"{name}: {(cnt, A, B, Cq, E0)} {r}"
+        assert 0 < ev[1] < ev[0] and ev[1] % n == 0, f"{name}: {r}"   # (2 * 2^range_exp: fewer terms per row than 64 *)
+        r.update(per_row=[int(e) // n for e in ev[:2]])
     return r

@@ -345,6 +345,21 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def rowreduce_entry_points(self):
+        """``pgb_row_reduce``, ``pgb_row_reduce_finish`` and ``pgb_row_reduce_workspace_bytes``
+        (include/pgbart_rowreduce.h): HIP library only, hence not in SYMBOLS."""
+        lib = self.lib
+        lib.pgb_row_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pgb_row_reduce.restype = C.c_int
+        lib.pgb_row_reduce_finish.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        lib.pgb_row_reduce_finish.restype = C.c_int
+        lib.pgb_row_reduce_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        lib.pgb_row_reduce_workspace_bytes.restype = C.c_int64
+        return lib.pgb_row_reduce, lib.pgb_row_reduce_finish, lib.pgb_row_reduce_workspace_bytes
+
     def chain_diag_entry_point(self):
         """``pgb_chain_diag`` (include/pgbart_diag.h): HIP library only, hence not in SYMBOLS.  A library without the
         symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""

@@ -228,12 +228,13 @@ class Job:
         lib.check(rc, "pgb_predict")
         return md
 
-    def blocks(self, be, bytes_per_row: int, y: bool = False, predict: bool = False):
+    def blocks(self, be, bytes_per_row: int, y: bool = False, predict: bool = False, reserved: int = 0):
         """Generator over the row blocks of the call (``PGB_PW_BLOCK_BYTES``): uploads the block's rows of ``X``, of
         ``y`` if asked to and of the offset, runs :meth:`predict` into ``md`` if asked to, and hands out the
-        :class:`Block`."""
+        :class:`Block`.  ``reserved``: device bytes the consumer holds across all blocks; they come off what a block
+        may take."""
         mem = be.mem
-        for r0, r1 in row_blocks(self.n, bytes_per_row, block_bytes(*PW_BLOCK)):
+        for r0, r1 in row_blocks(self.n, bytes_per_row, block_bytes(*PW_BLOCK) - int(reserved)):
             blk = Block(r0, r1, mem.from_host(self.X[r0:r1]))
             if y:
                 blk.yd = mem.from_host(self.y[r0:r1])

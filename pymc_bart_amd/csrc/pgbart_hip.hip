@@ -51,6 +51,7 @@
 #include "pgbart_psis.h"
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
+#include "pgbart_rowreduce.h"
 #include "pgbart_diag.h"
 #include "pgbart_ppc.h"
 #include "pgbart_shap.h"
@@ -82,3 +83,4 @@
 #include "k_pdp.h"
 #include "k_shap.h"
 #include "k_shap_interaction.h"
+#include "k_rowreduce.h"

@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""ms per call of the per-draw averages over rows on the device against what a user did before them, on one GPU.
+
+Per shape, on a real chain of ``sample_chain`` (data: ``workloads.cfg2``), from host arrays to host results, the median
+of ``--reps`` calls after one warm-up call:
+
+* ``average_prediction``  weighted means by 8 contiguous groups: per block of rows one ``pgb_predict`` into device
+                          scratch and one ``pgb_row_reduce`` on it; ``D x 8`` doubles reach the host.
+* ``average_contrast``    column 0 set to its 75 % and its 25 % quantile: two ``pgb_predict`` per block.
+* ``bayes_r2``            against the observations of the fit.
+* THE BASELINE            the route of the parent commit, whose ``sample_posterior`` is this tree's: every draw's
+                          predictions to the host (twice for the contrast), then NumPy -- the group sums as one matrix
+                          product with the weighted group indicators.  ``--host-reps`` calls (default 2: it is slow).
+* ``pgb_row_reduce``      the entry point alone on the resident predictions of the same shape, between two events of
+                          the stream: the clearing of the workspace, ``k_rowreduce`` and the entry point's wait for
+                          the stream.
+
+Shapes: ``plot`` (1000 rows x 10 columns, m = 50, 200 draws) and ``cfg2`` (100 k x 50, m = 200, 1000 draws).  Writes
+``profiles/rowreduce_timing.json`` (``--out``; shapes already in the file and not timed now are kept) with the
+kernel-resource rows of ``k_rowreduce`` and ``k_rowreduce_finish``, the largest relative difference between the device
+results and the baseline's, and prints it as one JSON line.  Nothing is required of the figures.
+
+  python tools/rowreduce_timing.py [--reps 5] [--host-reps 2] [--shapes plot,cfg2] [--out FILE]
+"""
+
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+SHAPES = {
+    "plot": dict(n=1000, p=10, m=50, draws=200),
+    "cfg2": dict(n=100_000, p=50, m=200, draws=1000),
+}
+GROUPS = 8
+
+
+def _fit(shape):
+    from pymc_bart_amd import BARTOp
+    from pymc_bart_amd.chains import sample_chain
+    from pymc_bart_amd.utils import _get_posterior_sampler
+    from pymc_bart_amd.workloads import cfg2
+
+    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
+    op = BARTOp(w["X"], w["Y"], m=w["m"])
+    t0 = time.perf_counter()
+    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
+    return w["X"], w["Y"], _get_posterior_sampler(op), time.perf_counter() - t0
+
+
+def _time(legs: dict, reps: int) -> dict:
+    import numpy as np
+    import torch
+
+    for f in legs.values():
+        f()
+    ms = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, f in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: {"median_ms": round(float(np.median(v)), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+            for k, v in ms.items()}
+
+
+def _kernel_alone(sampler, X, w, gid, reps):
+    """``pgb_row_reduce`` (workspace cleared, ``k_rowreduce``, the wait for the stream) on the resident predictions of
+    every draw at every row, by stream events."""
+    import numpy as np
+    import torch
+
+    from pymc_bart_amd import average
+
+    job = average.AverageJob(sampler, X, None, w, gid)
+    be = job.hip_backend("the timing of pgb_row_reduce runs")
+    lib, mem = be.lib, be.mem
+    n, D, K, p = job.n, job.D, job.K, job.p
+    xd = mem.from_host(job.X)
+    md = mem.empty((D * K * n,), np.float64)
+    carr = job.pool.as_c()
+    lib.check(lib.lib.pgb_predict(C.byref(carr), job.fidx.ctypes.data, D, job.m, mem.ptr(xd), n, p, p, None, 0, mem.ptr(md),
+                                  mem.stream_ptr), "pgb_predict")
+    wd, gd = mem.from_host(job.weights), mem.from_host(job.gid)
+    ws = mem.empty((job.ws_bytes // 8,), np.float64)
+    reduce_ = lib.rowreduce_entry_points()[0]
+    ev = []
+    for _ in range(reps + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        lib.check(reduce_(mem.ptr(md), None, D, K, n, n, mem.ptr(wd), mem.ptr(gd), None, None, None, None, job.G, job.code, 0, 1,
+                          mem.ptr(ws), None, mem.stream_ptr), "pgb_row_reduce")
+        b.record()
+        torch.cuda.synchronize()
+        ev.append(a.elapsed_time(b))
+    return float(np.median(ev[1:])), 8.0 * D * K * n
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host-reps", type=int, default=2)
+    ap.add_argument("--shapes", default="plot,cfg2")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "rowreduce_timing.json"))
+    args = ap.parse_args(argv)
+    names = [s for s in args.shapes.split(",") if s]
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.join(HERE, "tools"))
+    import numpy as np
+    import torch  # noqa: F401
+
+    import occupancy_guard
+    from pymc_bart_amd import average_contrast, average_prediction, bayes_r2
+
+    line = {"metric": "ms_per_call", "reps": args.reps, "host_reps": args.host_reps, "groups": GROUPS, "shapes": {},
+            "baseline": "sample_posterior of all draws to the host (twice for the contrast) + NumPy, in this process: the "
+                        "parent commit's sample_posterior is this tree's"}
+    if os.path.exists(args.out):
+        with open(args.out) as fh:
+            line["shapes"] = {k: v for k, v in json.load(fh).get("shapes", {}).items() if k not in names}
+    for name in names:
+        shape = SHAPES[name]
+        X, Y, sampler, secs = _fit(shape)
+        n, D = X.shape[0], sampler.n_draws
+        rng = np.random.default_rng(3)
+        w = rng.uniform(0.5, 1.5, n)
+        gid = (np.arange(n) * GROUPS // n).astype(np.int64)           # contiguous groups: the fast case
+        ind = np.zeros((n, GROUPS))
+        ind[np.arange(n), gid] = w
+        W = ind.sum(axis=0)
+        Xa, Xb = X.copy(), X.copy()
+        Xa[:, 0], Xb[:, 0] = np.quantile(X[:, 0], 0.75), np.quantile(X[:, 0], 0.25)
+        everything = list(range(D))
+        dev, host = {}, {}
+
+        def pull(M):
+            return np.asarray(sampler.sample_posterior(M, everything, None))[:, 0, :]           # (D, n)
+
+        def host_r2():
+            v = pull(X)
+            res = Y[None, :] - v
+            E = lambda t: (t @ ind) / W  # noqa: E731
+            mv, mr = E(v), E(res)
+            var_fit, var_res = E(v * v) - mv * mv, E(res * res) - mr * mr
+            host["bayes_r2"] = var_fit / (var_fit + var_res)
+
+        legs = {"average_prediction": lambda: dev.__setitem__("average_prediction", average_prediction(sampler, X, w, gid)["mean"][:, :, 0]),
+                "average_contrast": lambda: dev.__setitem__("average_contrast", average_contrast(sampler, Xa, Xb, w, gid)["mean"][:, :, 0]),
+                "bayes_r2": lambda: dev.__setitem__("bayes_r2", bayes_r2(sampler, X, Y, w, gid)["r2"])}
+        host_legs = {"average_prediction": lambda: host.__setitem__("average_prediction", (pull(X) @ ind) / W),
+                     "average_contrast": lambda: host.__setitem__("average_contrast", ((pull(Xa) - pull(Xb)) @ ind) / W),
+                     "bayes_r2": host_r2}
+        t_dev, t_host = _time(legs, args.reps), _time(host_legs, args.host_reps)
+        k_ms, k_bytes = _kernel_alone(sampler, X, w, gid, args.reps)
+        row = {"shape": dict(shape, chain_seconds=round(secs, 1)), "calls": {}}
+        for key in legs:
+            scale = np.max(np.abs(host[key]))
+            row["calls"][key] = {"device": t_dev[key], "host_route": t_host[key],
+                                 "speedup": round(t_host[key]["median_ms"] / t_dev[key]["median_ms"], 2),
+                                 "max_abs_difference_over_max_abs": float(np.max(np.abs(dev[key] - host[key])) / scale)}
+        row["pgb_row_reduce_ms"] = round(k_ms, 4)
+        row["pgb_row_reduce_share_of_average_prediction"] = round(k_ms / t_dev["average_prediction"]["median_ms"], 4)
+        row["pgb_row_reduce_read_GB_per_s"] = round(k_bytes / k_ms / 1e6, 1)
+        print(f"[rowreduce_timing] {name}: {json.dumps(row)}", file=sys.stderr, flush=True)
+        line["shapes"][name] = row
+        del X, Y, sampler, ind, dev, host
+    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_rowreduce")]
+    with open(args.out, "w") as fh:
+        json.dump(line, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(line))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

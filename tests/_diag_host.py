@@ -3,13 +3,10 @@ kernel compiles -- built with gcc like ``tests/_rowsummary_host.py``.  It export
 the columns of a matrix, and the pieces the exact tests look at."""
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import compiled
+from _host_build import build
 
 SHIM = r"""
 #include <stdint.h>
@@ -57,25 +54,13 @@ TRANSFORMS = {"identity": 0, "exp_shift": 1}
 ALL, MEAN_ONLY = 0, 1
 ROWS = ("rhat2_bulk", "rhat2_folded", "ess_bulk", "ess_tail_lo", "ess_tail_hi", "ess_mean", "mean", "var", "constant",
         "reserved")
-_LIB = None
+SIGNATURES = {"diag_columns": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_double, C.c_void_p]),
+              "diag_exp": (C.c_double, [C.c_double]), "diag_ranks": (None, [C.c_void_p, C.c_int, C.c_void_p])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_diag_host_")
-        src, so = os.path.join(d, "diag_host.c"), os.path.join(d, "diag_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.diag_columns.restype = C.c_int
-        L.diag_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                   C.c_double, C.c_void_p]
-        L.diag_exp.restype, L.diag_exp.argtypes = C.c_double, [C.c_double]
-        L.diag_ranks.restype, L.diag_ranks.argtypes = None, [C.c_void_p, C.c_int, C.c_void_p]
-        _LIB = L
-    return _LIB
+    return build("diag_host", SHIM, SIGNATURES)
 
 
 def max_draws() -> int:

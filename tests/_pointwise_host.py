@@ -2,13 +2,11 @@
 device kernels compile -- built with gcc the way ``pymc_bart_amd/compiled.py`` builds host code (its flags,
 ``-ffp-contract=off``).  It exports the header's ``pgb_logpdf`` over rows and its reduction over draws."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import _abi, compiled
+from _host_build import build
+from pymc_bart_amd import _abi
 
 SHIM = r"""
 #include <stdint.h>
@@ -48,26 +46,14 @@ void pw_reduce(const double* ll, int D, int64_t n, double* out) {
 double pw_clamp(double x) { return pgb_clamp_loglik(x); }
 """
 
-_LIB = None
+SIGNATURES = {"pw_logpdf_rows": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int64)]),
+              "pw_reduce": (None, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+              "pw_clamp": (C.c_double, [C.c_double])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_pw_host_")
-        src, so = os.path.join(d, "pw_host.c"), os.path.join(d, "pw_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.pw_logpdf_rows.restype = C.c_int
-        L.pw_logpdf_rows.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.POINTER(C.c_int64)]
-        L.pw_reduce.restype = None
-        L.pw_reduce.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
-        L.pw_clamp.restype, L.pw_clamp.argtypes = C.c_double, [C.c_double]
-        _LIB = L
-    return _LIB
+    return build("pw_host", SHIM, SIGNATURES)
 
 
 def chunk() -> int:

@@ -3,13 +3,11 @@ device kernel compiles -- built with gcc like ``tests/_rowsummary_host.py``.  It
 over a ``(D, K, n)`` array of predictors with the global index of its first row, the PIT counts and the flag counts.
 ``lib(max_tries=1)`` is a second build with ``-DPGB_PPC_MAX_TRIES=1``."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import _abi, compiled
+from _host_build import build
+from pymc_bart_amd import _abi
 
 SHIM = r"""
 #include <stdint.h>
@@ -60,25 +58,13 @@ int ppc_fill(int family, int K, const double* mu, int D, int64_t n, int64_t ld, 
 """
 
 FAMILIES = {k: v for k, v in _abi.FAMILIES.items() if k not in ("callback", "compiled")}
-_LIBS = {}
+SIGNATURES = {"ppc_fill": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+              "ppc_poisson_switch": (C.c_double, None), "ppc_max_rate": (C.c_double, None)}
 
 
 def lib(max_tries=None):
-    if max_tries not in _LIBS:
-        d = tempfile.mkdtemp(prefix="pgb_ppc_host_")
-        src, so = os.path.join(d, "ppc_host.c"), os.path.join(d, "ppc_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        extra = [] if max_tries is None else [f"-DPGB_PPC_MAX_TRIES={int(max_tries)}"]
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, *extra, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.ppc_fill.restype = C.c_int
-        L.ppc_fill.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int,
-                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ppc_poisson_switch.restype = C.c_double
-        L.ppc_max_rate.restype = C.c_double
-        _LIBS[max_tries] = L
-    return _LIBS[max_tries]
+    return build("ppc_host", SHIM, SIGNATURES, () if max_tries is None else (f"-DPGB_PPC_MAX_TRIES={int(max_tries)}",))
 
 
 def poisson_switch() -> float:

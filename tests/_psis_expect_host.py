@@ -2,13 +2,10 @@
 device kernel compiles -- built with gcc like ``tests/_psis_host.py``.  It exports the header's
 ``pgb_psis_row_expect`` over the columns of two matrices."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import compiled
+from _host_build import build
 
 SHIM = r"""
 #include <stdint.h>
@@ -38,25 +35,15 @@ int psis_expect_rows(const double* ll, int D, int64_t n, int64_t ld, int M, cons
 """
 
 KINDS = {"value": 0, "pit": 1}
-_LIB = None
+SIGNATURES = {"psis_expect_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_int, C.c_void_p]),
+              "psis_g_max": (C.c_double, None)}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_psis_expect_host_")
-        src, so = os.path.join(d, "psis_expect_host.c"), os.path.join(d, "psis_expect_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.psis_expect_rows.restype = C.c_int
-        L.psis_expect_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
-                                       C.c_int, C.c_void_p]
-        L.psis_g_max.restype = C.c_double
-        assert L.psis_kind_value() == KINDS["value"] and L.psis_kind_pit() == KINDS["pit"]
-        _LIB = L
-    return _LIB
+    L = build("psis_expect_host", SHIM, SIGNATURES)
+    assert L.psis_kind_value() == KINDS["value"] and L.psis_kind_pit() == KINDS["pit"]
+    return L
 
 
 def g_max() -> float:

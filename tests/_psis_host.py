@@ -2,13 +2,10 @@
 compiles -- built with gcc like ``tests/_pointwise_host.py``.  It exports the header's ``pgb_psis_row`` over the
 columns of a matrix."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import compiled
+from _host_build import build
 
 SHIM = r"""
 #include <stdint.h>
@@ -38,24 +35,12 @@ double psis_log1p(double x) { const pgb_lltabs tb = pgb_lltabs_default(); return
 double psis_expm1(double x) { const pgb_lltabs tb = pgb_lltabs_default(); return pgb_psis_expm1(x, &tb); }
 """
 
-_LIB = None
+SIGNATURES = {"psis_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+              **{f: (C.c_double, [C.c_double]) for f in ("psis_sqrt", "psis_log1p", "psis_expm1")}}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_psis_host_")
-        src, so = os.path.join(d, "psis_host.c"), os.path.join(d, "psis_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.psis_rows.restype = C.c_int
-        L.psis_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
-        for f in (L.psis_sqrt, L.psis_log1p, L.psis_expm1):
-            f.restype, f.argtypes = C.c_double, [C.c_double]
-        _LIB = L
-    return _LIB
+    return build("psis_host", SHIM, SIGNATURES)
 
 
 def max_draws() -> int:

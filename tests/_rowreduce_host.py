@@ -2,13 +2,10 @@
 the device kernels compile -- built with gcc like ``tests/_rowsummary_host.py``.  It exports the header's
 ``pgb_rowred_block`` and ``pgb_rowred_finish``."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import compiled
+from _host_build import build
 
 SHIM = r"""
 #include <stdint.h>
@@ -37,29 +34,17 @@ void rowred_call(const double* a, const double* b, int D, int K, int64_t n, int6
 """
 
 TRANSFORMS = {"identity": 0, "exp": 1, "logistic": 2, "probit": 3}
-_LIB = None
+P = C.c_void_p
+SIGNATURES = {"rowred_ws_doubles": (C.c_int64, [C.c_int] * 4),
+              "rowred_block": (None, [P, P, C.c_int, C.c_int, C.c_int64, C.c_int64, P, P, P, P, P, P, C.c_int, C.c_int, C.c_int64,
+                                      C.c_int, P, P]),
+              "rowred_finish": (None, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P]),
+              "rowred_call": (None, [P, P, C.c_int, C.c_int, C.c_int64, C.c_int64, P, P, P, P, P, P, C.c_int, C.c_int, P, P, P, P,
+                                     P])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_rowred_host_")
-        src, so = os.path.join(d, "rowred_host.c"), os.path.join(d, "rowred_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        P = C.c_void_p
-        L.rowred_ws_doubles.restype, L.rowred_ws_doubles.argtypes = C.c_int64, [C.c_int] * 4
-        L.rowred_block.restype = None
-        L.rowred_block.argtypes = [P, P, C.c_int, C.c_int, C.c_int64, C.c_int64, P, P, P, P, P, P, C.c_int, C.c_int, C.c_int64,
-                                   C.c_int, P, P]
-        L.rowred_finish.restype = None
-        L.rowred_finish.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P]
-        L.rowred_call.restype = None
-        L.rowred_call.argtypes = [P, P, C.c_int, C.c_int, C.c_int64, C.c_int64, P, P, P, P, P, P, C.c_int, C.c_int, P, P, P, P, P]
-        _LIB = L
-    return _LIB
+    return build("rowred_host", SHIM, SIGNATURES)
 
 
 def max_groups() -> int:

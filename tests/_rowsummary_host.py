@@ -2,13 +2,10 @@
 header the device kernel compiles -- built with gcc like ``tests/_psis_host.py``.  It exports the header's
 ``pgb_rowsum_column`` over the columns of a matrix."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-from pymc_bart_amd import compiled
+from _host_build import build
 
 SHIM = r"""
 #include <stdint.h>
@@ -55,26 +52,14 @@ double rowsum_value(double x, int transform) {
 """
 
 TRANSFORMS = {"identity": 0, "exp": 1, "logistic": 2, "probit": 3}
-_LIB = None
+SIGNATURES = {"rowsum_columns": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_int, C.c_void_p]),
+              "rowsum_sorted": (None, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+              "rowsum_value": (C.c_double, [C.c_double, C.c_int])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_rowsum_host_")
-        src, so = os.path.join(d, "rowsum_host.c"), os.path.join(d, "rowsum_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.rowsum_columns.restype = C.c_int
-        L.rowsum_columns.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                     C.c_int, C.c_void_p]
-        L.rowsum_sorted.restype = None
-        L.rowsum_sorted.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
-        L.rowsum_value.restype, L.rowsum_value.argtypes = C.c_double, [C.c_double, C.c_int]
-        _LIB = L
-    return _LIB
+    return build("rowsum_host", SHIM, SIGNATURES)
 
 
 def max_draws() -> int:

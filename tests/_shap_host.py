@@ -16,16 +16,14 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import math
-import os
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 
 import _predict_exact as ex
+from _host_build import build
 from _predict_exact import Leaf, Split
-from pymc_bart_amd import _abi, compiled
+from pymc_bart_amd import _abi
 
 SHIM = r"""
 #include <stdint.h>
@@ -84,28 +82,17 @@ MEMBER = np.dtype([("var", np.int32), ("rule", np.int32), ("side", np.int32), ("
 LEAF = np.dtype([("node", np.int32), ("first", np.int32), ("n_members", np.int32), ("n_groups", np.int32),
                  ("svar", np.int32), ("sgroup", np.int32), ("xbar", np.float64)])
 HEAD, TAIL = 1, 2
-_LIB = None
+SIGNATURES = {"shap_rows": (C.c_int, [C.POINTER(_abi.TreeArraysC), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                      C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+              "shap_records": (C.c_int, [C.POINTER(_abi.TreeArraysC), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+              "shap_weights": (None, [C.c_int, C.c_void_p])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_shap_host_")
-        src, so = os.path.join(d, "shap_host.c"), os.path.join(d, "shap_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.shap_rows.restype = C.c_int
-        L.shap_rows.argtypes = [C.POINTER(_abi.TreeArraysC), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64,
-                                C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.shap_records.restype = C.c_int
-        L.shap_records.argtypes = [C.POINTER(_abi.TreeArraysC), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                   C.c_void_p, C.c_void_p, C.c_void_p]
-        L.shap_weights.restype, L.shap_weights.argtypes = None, [C.c_int, C.c_void_p]
-        assert L.shap_member_bytes() == MEMBER.itemsize and L.shap_leaf_bytes() == LEAF.itemsize
-        _LIB = L
-    return _LIB
+    L = build("shap_host", SHIM, SIGNATURES)
+    assert L.shap_member_bytes() == MEMBER.itemsize and L.shap_leaf_bytes() == LEAF.itemsize
+    return L
 
 
 def max_u() -> int:

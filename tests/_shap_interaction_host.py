@@ -15,16 +15,14 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import math
-import os
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 
 import _predict_exact as ex
 import _shap_host as host
-from pymc_bart_amd import _abi, compiled
+from _host_build import build
+from pymc_bart_amd import _abi
 
 SHIM = r"""
 #include <stdint.h>
@@ -77,24 +75,14 @@ int shapx_rows(const pgb_tree_arrays* trees, const int32_t* fidx, int m, const d
 }
 """
 
-_LIB = None
+SIGNATURES = {"shapx_rows": (C.c_int, [C.POINTER(_abi.TreeArraysC), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                       C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p]),
+              "shapx_slots": (C.c_int, [C.POINTER(_abi.TreeArraysC), C.c_int])}
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        d = tempfile.mkdtemp(prefix="pgb_shapx_host_")
-        src, so = os.path.join(d, "shapx_host.c"), os.path.join(d, "shapx_host.so")
-        with open(src, "w") as fh:
-            fh.write(SHIM)
-        subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", src, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.shapx_rows.restype = C.c_int
-        L.shapx_rows.argtypes = [C.POINTER(_abi.TreeArraysC), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64,
-                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.shapx_slots.restype, L.shapx_slots.argtypes = C.c_int, [C.POINTER(_abi.TreeArraysC), C.c_int]
-        _LIB = L
-    return _LIB
+    return build("shapx_host", SHIM, SIGNATURES)
 
 
 def max_u() -> int:

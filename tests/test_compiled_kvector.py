@@ -12,6 +12,7 @@ import warnings
 import numpy as np
 import pytest
 
+from _host_build import build
 from pymc_bart_amd import CompiledLikelihood, _abi, compiled
 from pymc_bart_amd.compiled import CompileError, compile_loglik
 from pymc_bart_amd.pgbart import PGBART, BARTOp
@@ -118,15 +119,9 @@ void spec_rows(int which, int K, const double* y, const double* mu, int64_t n, d
 """
 
 
-def _spec_lib(tmp_path):
-    src = tmp_path / "spec_rows.c"
-    src.write_text(_SPEC_HARNESS)
-    so = tmp_path / "spec_rows.so"
-    subprocess.check_call(["gcc", *compiled.HOST_FLAGS, f"-I{compiled.INCLUDE}", str(src), "-o", str(so), "-lm"])
-    f = C.CDLL(str(so)).spec_rows
-    f.restype = None
-    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    return f
+def _spec_lib():
+    return build("spec_rows", _SPEC_HARNESS,
+                 {"spec_rows": (None, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])}).spec_rows
 
 
 def _edge_grid(K, n, seed, classes=False):
@@ -145,8 +140,8 @@ def _edge_grid(K, n, seed, classes=False):
 
 
 @pytest.mark.parametrize("which, K", [(0, 2), (1, 2), (1, 3), (1, 4), (1, 6), (1, 12), (1, 16)])
-def test_host_builds_of_the_restated_bodies_equal_the_spec_bit_for_bit(which, K, tmp_path):
-    spec = _spec_lib(tmp_path)
+def test_host_builds_of_the_restated_bodies_equal_the_spec_bit_for_bit(which, K):
+    spec = _spec_lib()
     y, mu = _edge_grid(K, 40_000, seed=10 * which + K, classes=which == 1)
     want = np.empty(y.size)
     spec(which, K, y.ctypes.data, mu.ctypes.data, y.size, want.ctypes.data)

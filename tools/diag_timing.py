@@ -25,14 +25,12 @@ with the kernel-resource row of ``k_chain_diag`` and prints it as one JSON line.
 
 from __future__ import annotations
 
-import argparse
-import ctypes as C
 import json
 import os
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
+from _timing import HERE
 
 SHAPES = {
     "small": dict(n=2000, p=10, m=50, chains=4, draws=250),
@@ -40,97 +38,50 @@ SHAPES = {
 }
 
 
-def _fit(shape):
-    import numpy as np
-
-    from pymc_bart_amd import BARTOp, NormalLikelihood
-    from pymc_bart_amd.chains import attach_history, sample_chain
-    from pymc_bart_amd.utils import _get_posterior_sampler
-    from pymc_bart_amd.workloads import cfg2
-
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    chains = [sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, chain=c, keep_draws=False)
-              for c in range(shape["chains"])]
-    secs = time.perf_counter() - t0
-    attach_history(op, chains)
-    sigma = np.concatenate([c["sigma"] for c in chains])
-    return w["X"], np.asarray(w["Y"], np.float64), _get_posterior_sampler(op), {"sigma": sigma}, NormalLikelihood("sigma"), secs
-
-
-def _time(f, reps: int, warm: bool = True) -> dict:
-    import numpy as np
-    import torch
-
-    if warm:
-        f()
-    ms = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        f()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": round(float(np.median(ms)), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
-
-
 def _kernel_alone(sampler, X, n_chains, npc, reps):
     """``pgb_chain_diag`` on the resident predictions of every draw at every row, by stream events."""
     import numpy as np
-    import torch
 
     from pymc_bart_amd import diagnostics, summary
 
     job = summary.SummaryJob(sampler, X, None, None, None, "identity", None, None)
-    be = job.backend()
-    lib, mem = be.lib, be.mem
-    n, D, K, p = job.n, job.D, job.K, job.p
-    xd = mem.from_host(job.X)
-    md = mem.empty((D * K * n,), np.float64)
-    carr = job.pool.as_c()
-    lib.check(lib.lib.pgb_predict(C.byref(carr), job.fidx.ctypes.data, D, job.m, mem.ptr(xd), n, p, p, None, 0, mem.ptr(md),
-                                  mem.stream_ptr), "pgb_predict")
+    res = _timing.resident_predictions(job)
+    lib, mem = res.backend.lib, res.backend.mem
+    n, K = job.n, job.K
     S = diagnostics.kept_draws(n_chains, npc)
     z = diagnostics.z_table(S)
     od = mem.empty((diagnostics.NOUT * K * n,), np.float64)
     call = lib.chain_diag_entry_point()
-    ev = []
-    for _ in range(reps + 1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        lib.check(call(mem.ptr(md), n_chains, npc, K * n, K * n, 0, diagnostics.ALL, z.ctypes.data, 1.0 / np.log10(S),
-                       mem.ptr(od), mem.stream_ptr), "pgb_chain_diag")
-        b.record()
-        torch.cuda.synchronize()
-        ev.append(a.elapsed_time(b))
-    return float(np.median(ev[1:])), mem.to_host(od).reshape(diagnostics.NOUT, K, n)
+    ms = _timing.events_ms(lambda: lib.check(call(mem.ptr(res.pred), n_chains, npc, K * n, K * n, 0, diagnostics.ALL,
+                                                  z.ctypes.data, 1.0 / np.log10(S), mem.ptr(od), mem.stream_ptr),
+                                             "pgb_chain_diag"), reps)
+    return ms, mem.to_host(od).reshape(diagnostics.NOUT, K, n)
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=3)
+    ap = _timing.base_parser("diag_timing.json", "small,cfg2", reps=3)
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--host-rows", type=int, default=2000)
-    ap.add_argument("--shapes", default="small,cfg2")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "diag_timing.json"))
     args = ap.parse_args(argv)
     names = [s for s in args.shapes.split(",") if s]
-    sys.path[:0] = [HERE, os.path.join(HERE, "tools"), os.path.join(HERE, "tests")]
+    sys.path[:0] = [HERE, os.path.join(HERE, "tests")]
     import numpy as np
     import torch  # noqa: F401
 
     import _diag_numpy as restatement
-    import occupancy_guard
-    from pymc_bart_amd import convergence, pointwise_log_likelihood, relative_efficiency
+    from pymc_bart_amd import NormalLikelihood, convergence, pointwise_log_likelihood, relative_efficiency
+    from pymc_bart_amd.utils import _get_posterior_sampler
 
-    line = {"metric": "ms_per_call", "reps": args.reps, "host_reps": args.host_reps, "shapes": {}}
-    if os.path.exists(args.out):
-        with open(args.out) as fh:
-            line["shapes"] = {k: v for k, v in json.load(fh).get("shapes", {}).items() if k not in names}
+    def one(f, reps, warm=True):
+        return _timing.time_legs({"leg": f}, reps, warm)["leg"]
+
+    line = {"metric": "ms_per_call", "reps": args.reps, "host_reps": args.host_reps,
+            "shapes": _timing.kept_shapes(args.out, names)}
     for name in names:
         shape = SHAPES[name]
-        X, y, sampler, pts, lik, secs = _fit(shape)
+        f = _timing.fit(shape, chains=shape["chains"])
+        X, y, sampler, secs = f.X, np.asarray(f.Y, np.float64), _get_posterior_sampler(f.op), f.seconds
+        pts, lik = {"sigma": np.concatenate([c["sigma"] for c in f.results])}, NormalLikelihood("sigma")
         n, nc, npc = X.shape[0], shape["chains"], shape["draws"]
         last = {}
 
@@ -140,7 +91,7 @@ def main(argv=None) -> int:
         def leg_reff():
             last["reff"] = relative_efficiency(sampler, X, y, lik, points=pts)
 
-        row = {"shape": dict(shape, chain_seconds=round(secs, 1)), "convergence": _time(leg_convergence, args.reps)}
+        row = {"shape": dict(shape, chain_seconds=round(secs, 1)), "convergence": one(leg_convergence, args.reps)}
         k_ms, stats = _kernel_alone(sampler, X, nc, npc, args.reps)
         res = last["res"]
         row["k_chain_diag_ms"] = round(k_ms, 3)
@@ -163,8 +114,8 @@ def main(argv=None) -> int:
             pred = keep["pred"]
             keep["host"] = restatement.columns(np.ascontiguousarray(pred.reshape(pred.shape[0], -1)[:, :rows]), nc)
 
-        t_host = _time(leg_to_host, args.host_reps, warm=False)
-        t_np = _time(leg_numpy, args.host_reps, warm=False)
+        t_host = one(leg_to_host, args.host_reps, warm=False)
+        t_np = one(leg_numpy, args.host_reps, warm=False)
         scale = n * sampler.n_outputs / rows
         host_ms = t_host["median_ms"] + t_np["median_ms"] * scale
         row["host_route"] = {"sample_posterior_to_host": t_host, "numpy_diagnostics": t_np, "numpy_rows_timed": rows,
@@ -176,26 +127,21 @@ def main(argv=None) -> int:
         row["ess_bulk_max_rel_diff_to_the_restatement"] = float(np.max(np.abs(got / keep["host"][2][:rows] - 1.0)))
         keep.clear()
         # r_eff against the matrix it would otherwise be computed from
-        row["relative_efficiency"] = _time(leg_reff, args.reps)
+        row["relative_efficiency"] = one(leg_reff, args.reps)
 
         def leg_matrix():
             keep["ll"] = pointwise_log_likelihood(sampler, X, y, lik, points=pts)
 
-        row["pointwise_log_likelihood_to_host"] = _time(leg_matrix, args.host_reps, warm=False)
+        row["pointwise_log_likelihood_to_host"] = one(leg_matrix, args.host_reps, warm=False)
         keep.clear()
         reff = last["reff"]
         row["reff"] = {"reff": reff["reff"], "reff_min": reff["reff_min"], "n_clamped": reff["n_clamped"]}
         line["shapes"][name] = row
         print(f"[diag_timing] {name}: {json.dumps(row)}", file=sys.stderr, flush=True)
-        with open(args.out, "w") as fh:   # (after every shape: a visit that ends early keeps what it has)
-            json.dump(line, fh, indent=1)
-            fh.write("\n")
-        del X, y, sampler, last
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"] == "k_chain_diag"]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+        _timing.write(args.out, line, echo=False)   # (after every shape: a visit that ends early keeps what it has)
+        del X, y, sampler, last, f
+    line["kernels"] = _timing.kernel_rows(lambda k: k == "k_chain_diag")
+    _timing.write(args.out, line)
     return 0
 
 

@@ -12,7 +12,7 @@ THE BASELINE is the same call of the package found in ``--baseline-root DIR`` (a
 in a process of its own, two legs (``ice`` / ``ice_again``) so that its run-to-run spread is on record.  Required: the
 new call is below the baseline at both shapes by more than the baseline's own spread.
 
-Also recorded, per shape: ``k_ice`` alone between two HIP events (``PGB_WALK_TIMING``, ``pgb_walk_kernel_ms``) as tree
+Also recorded, per shape: ``k_ice`` alone between two HIP events (``_timing.walk_timing()``, ``pgb_walk_kernel_ms``) as tree
 traversals/s, next to ``k_predict``'s rate for the same traversal count in the same process: one curve's probe matrix,
 resident, predicted for as many draws as the sweep has curves x samples.
 
@@ -23,15 +23,12 @@ Writes ``profiles/ice_timing.json`` (``--out``) and prints it as one JSON line.
 
 from __future__ import annotations
 
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
 
 SHAPES = {
     "plot": dict(n=1000, p=10, m=50, draws=500, var_idx=None, instances=30, samples=100),
@@ -39,35 +36,7 @@ SHAPES = {
 }
 
 
-def _fit(shape):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
-    from pymc_bart_amd.workloads import cfg2
-
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
-    return w["X"], op, time.perf_counter() - t0
-
-
-def _time(legs: dict, reps: int) -> dict:
-    import numpy as np
-    import torch
-
-    for f in legs.values():
-        f()
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": {k: round(float(np.median(v)), 3) for k, v in ms.items()},
-            "min_ms": {k: round(min(v), 3) for k, v in ms.items()},
-            "max_ms": {k: round(max(v), 3) for k, v in ms.items()}}
+LEGS = ("ice", "ice_again")
 
 
 def _call(op, X, shape):
@@ -87,9 +56,9 @@ def baseline(names, reps) -> dict:
     out = {"has_ice_module": os.path.exists(os.path.join(os.path.dirname(pymc_bart_amd.__file__), "ice.py"))}
     for name in names:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        out[name] = _time({"ice": lambda: _call(op, X, shape), "ice_again": lambda: _call(op, X, shape)}, reps)
-        out[name]["chain_seconds"] = round(secs, 1)
+        f = _timing.fit(shape)
+        out[name] = _timing.by_statistic(_timing.time_legs(dict.fromkeys(LEGS, lambda: _call(f.op, f.X, shape)), reps))
+        out[name]["chain_seconds"] = round(f.seconds, 1)
     return out
 
 
@@ -114,8 +83,7 @@ def _kernel_rates(op, X, shape, reps):
     probe = X.copy()
     probe[:, [v for v in range(p) if v != cols[0]]] = X[chosen[0], [v for v in range(p) if v != cols[0]]]
     probe_rows = part.resident_rows(probe)
-    os.environ["PGB_WALK_TIMING"] = "1"
-    try:
+    with _timing.walk_timing():
         ice, pred = [], []
         for _ in range(reps + 1):
             v = C.c_double(-1.0)
@@ -125,8 +93,6 @@ def _kernel_rates(op, X, shape, reps):
             part.sample_posterior(probe_rows, picks.ravel().tolist(), None)
             ms_of(C.byref(v))
             pred.append(v.value)
-    finally:
-        del os.environ["PGB_WALK_TIMING"]
     ice_ms, pred_ms = float(np.median(ice[1:])), float(np.median(pred[1:]))
     trav_ice = float(picks.size) * n * op.m
     trav_pred = trav_ice
@@ -138,40 +104,27 @@ def _kernel_rates(op, X, shape, reps):
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="plot,large")
-    ap.add_argument("--baseline-root", default=None, help="a built checkout of the parent commit: the baseline's package")
-    ap.add_argument("--baseline-leg", action="store_true", help=argparse.SUPPRESS)  # (the child process of --baseline-root)
-    ap.add_argument("--root", default=HERE, help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "ice_timing.json"))
-    args = ap.parse_args(argv)
+    args = _timing.base_parser("ice_timing.json", "plot,large", baseline=True).parse_args(argv)
     names = [s for s in args.shapes.split(",") if s]
     sys.path.insert(0, os.path.abspath(args.root))
     if args.baseline_leg:
-        print("BASELINE " + json.dumps(baseline(names, args.reps)), flush=True)
+        _timing.print_baseline(baseline(names, args.reps))
         return 0
-    sys.path.insert(0, os.path.join(HERE, "tools"))
     import torch  # noqa: F401
-
-    import occupancy_guard
 
     line = {"metric": "ms_per_call", "reps": args.reps, "shapes": {}}
     new = {}
     for name in names:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        t = _time({"ice": lambda: _call(op, X, shape)}, args.reps)
-        new[name] = {"shape": dict(shape, chain_seconds=round(secs, 1)),
-                     "median_ms": t["median_ms"]["ice"], "min_ms": t["min_ms"]["ice"], "max_ms": t["max_ms"]["ice"],
+        f = _timing.fit(shape)
+        X, op = f.X, f.op
+        t = _timing.time_legs({"ice": lambda: _call(op, X, shape)}, args.reps)["ice"]
+        new[name] = {"shape": dict(shape, chain_seconds=round(f.seconds, 1)), **t,
                      "kernels_alone": _kernel_rates(op, X, shape, args.reps)}
         print(f"[ice_timing] {name}: {json.dumps(new[name])}", file=sys.stderr, flush=True)
-        del X, op
+        del X, op, f
     if args.baseline_root:
-        cmd = [sys.executable, os.path.abspath(__file__), "--baseline-leg", "--root", os.path.abspath(args.baseline_root),
-               "--reps", str(args.reps), "--shapes", ",".join(names)]
-        txt = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=1100).stdout
-        base = json.loads([ln for ln in txt.splitlines() if ln.startswith("BASELINE ")][-1][9:])
+        base = _timing.run_baseline(__file__, args.baseline_root, ["--reps", str(args.reps), "--shapes", ",".join(names)])
         where = "a checkout of the parent commit, in a process of its own"
     else:
         base, where = None, None
@@ -181,19 +134,15 @@ def main(argv=None) -> int:
         if base is not None:
             b = base[name]
             bm = b["median_ms"]
-            spread = max(abs(bm["ice"] - bm["ice_again"]),
-                         max(b["max_ms"][k] - b["min_ms"][k] for k in ("ice", "ice_again")))
+            spread = _timing.spread(b, LEGS)
             row["baseline"] = {"measured_on": where, "has_ice_module": base["has_ice_module"], **b}
             row["baseline_spread_ms"] = round(spread, 3)
             row["speedup"] = round(min(bm.values()) / row["median_ms"], 2)
             ok[name] = bool(row["median_ms"] < min(bm.values()) - spread)
         line["shapes"][name] = row
     line["required"] = {"below_the_baseline_by_more_than_its_spread": ok} if base is not None else None
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_ice<")]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+    line["kernels"] = _timing.kernel_rows("k_ice<")
+    _timing.write(args.out, line)
     return 0 if all(ok.values()) else 1
 
 

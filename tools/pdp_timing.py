@@ -14,7 +14,7 @@ THE BASELINE is the same call of the package found in ``--baseline-root DIR`` (a
 in a process of its own, two legs (``pdp`` / ``pdp_again``) so that its run-to-run spread is on record.  Required: at
 ``plot`` the new call is not slower than the baseline beyond that spread.  At ``insample`` the ratio is reported.
 
-Also recorded, per shape: ``k_pdp_walk`` and ``k_pdp_lookup`` alone between stream events (``PGB_WALK_TIMING``,
+Also recorded, per shape: ``k_pdp_walk`` and ``k_pdp_lookup`` alone between stream events (``_timing.walk_timing()``,
 ``pgb_pdp_kernel_ms``) under ``route=1`` and ``route=2``; at the ``insample`` fit the same for growing row counts -- the
 crossover of the two routes; and the kernels' resource rows.
 
@@ -25,15 +25,12 @@ Writes ``profiles/pdp_timing.json`` (``--out``) and prints it as one JSON line.
 
 from __future__ import annotations
 
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
 
 SHAPES = {
     "plot": dict(n=1000, p=10, m=50, draws=500, var_idx=None, xs_interval="quantiles", samples=200, summary=False),
@@ -43,35 +40,7 @@ SHAPES = {
 CROSSOVER_ROWS = (64, 256, 1024, 4096, 16384, 65536)
 
 
-def _fit(shape):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
-    from pymc_bart_amd.workloads import cfg2
-
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
-    return w["X"], op, time.perf_counter() - t0
-
-
-def _time(legs: dict, reps: int) -> dict:
-    import numpy as np
-    import torch
-
-    for f in legs.values():
-        f()
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": {k: round(float(np.median(v)), 3) for k, v in ms.items()},
-            "min_ms": {k: round(min(v), 3) for k, v in ms.items()},
-            "max_ms": {k: round(max(v), 3) for k, v in ms.items()}}
+LEGS = ("pdp", "pdp_again")
 
 
 def _call(op, X, shape, lean: bool):
@@ -96,9 +65,9 @@ def baseline(names, reps) -> dict:
     lean = out["has_pdp_module"]
     for name in names:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        out[name] = _time({"pdp": lambda: _call(op, X, shape, lean), "pdp_again": lambda: _call(op, X, shape, lean)}, reps)
-        out[name]["chain_seconds"] = round(secs, 1)
+        f = _timing.fit(shape)
+        out[name] = _timing.by_statistic(_timing.time_legs(dict.fromkeys(LEGS, lambda: _call(f.op, f.X, shape, lean)), reps))
+        out[name]["chain_seconds"] = round(f.seconds, 1)
     return out
 
 
@@ -110,8 +79,7 @@ def _kernels_alone(s, rows, cols, picks, reps):
     ms_of = lib.lib.pgb_pdp_kernel_ms
     ms_of.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     out = {}
-    os.environ["PGB_WALK_TIMING"] = "1"
-    try:
+    with _timing.walk_timing():
         for route, name in ((1, "direct"), (2, "profile")):
             walk, look, taken = [], [], []
             for _ in range(reps + 1):
@@ -124,8 +92,6 @@ def _kernels_alone(s, rows, cols, picks, reps):
             out[name] = {"k_pdp_walk_ms": round(float(np.median(walk[1:])), 4),
                          "k_pdp_lookup_ms": round(float(np.median(look[1:])), 4) if look[-1] >= 0 else None,
                          "columns_on_the_profile_route": sum(r == 2 for t in taken for r in t[4]), "blocks": len(taken)}
-    finally:
-        del os.environ["PGB_WALK_TIMING"]
     return out
 
 
@@ -159,40 +125,27 @@ def _kernel_section(op, X, shape, reps, crossover: bool):
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="plot,insample")
-    ap.add_argument("--baseline-root", default=None, help="a built checkout of the parent commit: the baseline's package")
-    ap.add_argument("--baseline-leg", action="store_true", help=argparse.SUPPRESS)  # (the child process of --baseline-root)
-    ap.add_argument("--root", default=HERE, help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "pdp_timing.json"))
-    args = ap.parse_args(argv)
+    args = _timing.base_parser("pdp_timing.json", "plot,insample", baseline=True).parse_args(argv)
     names = [s for s in args.shapes.split(",") if s]
     sys.path.insert(0, os.path.abspath(args.root))
     if args.baseline_leg:
-        print("BASELINE " + json.dumps(baseline(names, args.reps)), flush=True)
+        _timing.print_baseline(baseline(names, args.reps))
         return 0
-    sys.path.insert(0, os.path.join(HERE, "tools"))
     import torch  # noqa: F401
-
-    import occupancy_guard
 
     line = {"metric": "ms_per_call", "reps": args.reps, "shapes": {}}
     new = {}
     for name in names:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        t = _time({"pdp": lambda: _call(op, X, shape, True)}, args.reps)
-        new[name] = {"shape": dict(shape, chain_seconds=round(secs, 1)),
-                     "median_ms": t["median_ms"]["pdp"], "min_ms": t["min_ms"]["pdp"], "max_ms": t["max_ms"]["pdp"],
+        f = _timing.fit(shape)
+        X, op = f.X, f.op
+        t = _timing.time_legs({"pdp": lambda: _call(op, X, shape, True)}, args.reps)["pdp"]
+        new[name] = {"shape": dict(shape, chain_seconds=round(f.seconds, 1)), **t,
                      "kernels_alone": _kernel_section(op, X, shape, args.reps, crossover=name == "insample")}
         print(f"[pdp_timing] {name}: {json.dumps(new[name])}", file=sys.stderr, flush=True)
-        del X, op
+        del X, op, f
     if args.baseline_root:
-        cmd = [sys.executable, os.path.abspath(__file__), "--baseline-leg", "--root", os.path.abspath(args.baseline_root),
-               "--reps", str(args.reps), "--shapes", ",".join(names)]
-        txt = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=1100).stdout
-        base = json.loads([ln for ln in txt.splitlines() if ln.startswith("BASELINE ")][-1][9:])
+        base = _timing.run_baseline(__file__, args.baseline_root, ["--reps", str(args.reps), "--shapes", ",".join(names)])
         where = "a checkout of the parent commit, in a process of its own"
     else:
         base, where = None, None
@@ -202,7 +155,7 @@ def main(argv=None) -> int:
         if base is not None:
             b = base[name]
             bm = b["median_ms"]
-            spread = max(abs(bm["pdp"] - bm["pdp_again"]), max(b["max_ms"][k] - b["min_ms"][k] for k in ("pdp", "pdp_again")))
+            spread = _timing.spread(b, LEGS)
             row["baseline"] = {"measured_on": where, "has_pdp_module": base["has_pdp_module"], **b}
             row["baseline_spread_ms"] = round(spread, 3)
             row["speedup"] = round(min(bm.values()) / row["median_ms"], 2)
@@ -210,11 +163,8 @@ def main(argv=None) -> int:
                 ok[name] = bool(row["median_ms"] <= max(bm.values()) + spread)
         line["shapes"][name] = row
     line["required"] = {"plot_not_slower_than_the_baseline_beyond_its_spread": ok} if base is not None else None
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_pdp_")]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+    line["kernels"] = _timing.kernel_rows("k_pdp_")
+    _timing.write(args.out, line)
     return 0 if all(ok.values()) else 1
 
 

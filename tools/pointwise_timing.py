@@ -24,33 +24,20 @@ Writes ``profiles/pointwise_timing.json`` (``--out``) and prints it as one JSON 
 
 from __future__ import annotations
 
-import argparse
 import ctypes as C
-import json
 import os
 import sys
 import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import numpy as np
+
+import _timing
+from _timing import HERE as ROOT
+
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import numpy as np  # noqa: E402
 
 NORMAL_BODY = "double z = (y - mu) / s;  return (-log(s) - 9.1893853320467274e-01) - 0.5 * (z * z);"
 PROBIT_BODY = "return log_ndtr(y > 0.5 ? mu : -mu);"
-
-
-def _chain(w, D, likelihood, tune, particles):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
-    from pymc_bart_amd.trees import PosteriorSampler
-
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    res = sample_chain(op, tune, D, num_particles=particles, random_seed=7, keep_draws=False, likelihood=likelihood)
-    base, batches = res["history"]
-    return PosteriorSampler.from_history(batches, base, w["m"], 1), res
 
 
 def _probe_sampler(body, names, values):
@@ -67,21 +54,22 @@ def _probe_sampler(body, names, values):
     return s
 
 
-def time_shape(name, w, D, family, reps, tune, particles, ab_lib=None) -> dict:
+def time_shape(name, workload, n, D, family, reps, tune, particles, ab_lib=None) -> dict:
     import torch
 
     from pymc_bart_amd import BernoulliLikelihood, NormalLikelihood, _abi
     from pymc_bart_amd.sampler import default_backend
+    from pymc_bart_amd.trees import PosteriorSampler
 
     be = default_backend()
     lib, mem = be.lib, be.mem
     lik = NormalLikelihood("sigma") if family == "normal" else BernoulliLikelihood("probit")
-    t0 = time.perf_counter()
-    ps, res = _chain(w, D, None if family == "normal" else lik, tune, particles)
-    chain_s = time.perf_counter() - t0
-    X, y = np.ascontiguousarray(w["X"], np.float64), np.ascontiguousarray(w["Y"], np.float64)
+    f = _timing.fit(dict(workload=workload, n=n, draws=D, likelihood=None if family == "normal" else lik), tune=tune,
+                    particles=particles)
+    res, m = f.results[0], f.op.m
+    ps = PosteriorSampler.from_history(res["history"][1], res["history"][0], m, 1)
+    X, y = np.ascontiguousarray(f.X, np.float64), np.ascontiguousarray(f.Y, np.float64)
     n, p = X.shape
-    m = w["m"]
     fidx = np.ascontiguousarray(ps.forest_idx[:D], np.int32)
     carr = ps.pool.as_c()
     sigma = float(np.median(res["sigma"])) if family == "normal" else 1.0
@@ -125,25 +113,16 @@ def time_shape(name, w, D, family, reps, tune, particles, ab_lib=None) -> dict:
     if ab_lib is not None:
         legs["ab_fused_matrix"] = fused(ab_lib, True)
         legs["ab_fused_summary"] = fused(ab_lib, False)
-    for f in legs.values():                               # warm every shape
-        f()
-        f()
+    for leg in legs.values():                             # warm every shape (and once more in time_legs)
+        leg()
     torch.cuda.synchronize()
     same = bool(torch.equal(ll, ll_unfused))
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    med = {k: float(np.median(v)) for k, v in ms.items()}
+    t = _timing.time_legs(legs, reps)
+    med = {k: v["median_ms"] for k, v in t.items()}
     spread = abs(med["predict"] - med["predict_again"])
-    worst = max(max(ms["predict"]) - min(ms["predict"]), max(ms["predict_again"]) - min(ms["predict_again"]))
-    out = {"shape": name, "n": n, "p": p, "m": m, "draws": D, "family": lik.family, "chain_seconds": round(chain_s, 1),
-           "median_ms": {k: round(v, 3) for k, v in med.items()},
-           "min_ms": {k: round(min(v), 3) for k, v in ms.items()},
+    worst = max(t[k]["max_ms"] - t[k]["min_ms"] for k in ("predict", "predict_again"))
+    out = {"shape": name, "n": n, "p": p, "m": m, "draws": D, "family": lik.family, "chain_seconds": round(f.seconds, 1),
+           "median_ms": med, "min_ms": {k: v["min_ms"] for k, v in t.items()},
            "predict_spread_ms": {"between_the_two_legs": round(spread, 3), "within_a_leg_max_minus_min": round(worst, 3)},
            "fused_matrix_equals_unfused_bits": same, "n_clamped": int(nc.value),
            "fused_summary_over_predict": round(med["fused_summary"] / med["predict"], 3),
@@ -157,20 +136,14 @@ def time_shape(name, w, D, family, reps, tune, particles, ab_lib=None) -> dict:
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
+    ap = _timing.base_parser("pointwise_timing.json", "cfg2,cfg4", reps=7)
     ap.add_argument("--tune", type=int, default=10)
     ap.add_argument("--particles", type=int, default=10)
-    ap.add_argument("--shapes", default="cfg2,cfg4")
     ap.add_argument("--small", action="store_true", help="a tenth of the rows (a quick look, not the record)")
     ap.add_argument("--ab-lib", default=None, help="a second build of the library for the table-placement A/B")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pointwise_timing.json"))
     args = ap.parse_args(argv)
     os.environ.setdefault("PGB_JIT_CACHE", tempfile.mkdtemp(prefix="pgb_jit_timing_"))
-    import occupancy_guard
-
     from pymc_bart_amd import _abi
-    from pymc_bart_amd.workloads import cfg2, cfg4
 
     import torch  # noqa: F401  (first: the libraries share its HIP runtime)
 
@@ -179,18 +152,14 @@ def main(argv=None) -> int:
     shapes = []
     for s in args.shapes.split(","):
         if s == "cfg2":
-            shapes.append(time_shape("cfg2-shaped", cfg2(n=100_000 // scale), 100, "normal", args.reps, args.tune,
+            shapes.append(time_shape("cfg2-shaped", "cfg2", 100_000 // scale, 100, "normal", args.reps, args.tune,
                                      args.particles, ab))
         elif s == "cfg4":
-            shapes.append(time_shape("cfg4-shaped", cfg4(n=1_000_000 // scale), 32, "bernoulli_probit", args.reps,
+            shapes.append(time_shape("cfg4-shaped", "cfg4", 1_000_000 // scale, 32, "bernoulli_probit", args.reps,
                                      args.tune, args.particles, ab))
-    kernels = [r for r in occupancy_guard.table() if r["kernel"].startswith(("k_pointwise", "k_predict"))]
     line = {"metric": "ms_per_call", "reps": args.reps, "small": bool(args.small), "ab_lib": args.ab_lib,
-            "shapes": shapes, "kernels": kernels}
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+            "shapes": shapes, "kernels": _timing.kernel_rows(("k_pointwise", "k_predict"))}
+    _timing.write(args.out, line)
     return 0
 
 

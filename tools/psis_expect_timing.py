@@ -25,17 +25,15 @@ Writes ``profiles/psis_expect_timing.json`` (``--out``) with the kernel-resource
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import subprocess
 import sys
 import tempfile
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(HERE, "tools"))
+import _timing
+from _timing import HERE
+from psis_timing import _fit, baseline_argv, parser
 
-from psis_timing import _fit, _time  # noqa: E402
+LEGS = ("matrices_to_host", "matrices_to_host_again")
 
 
 def baseline(args) -> dict:
@@ -51,7 +49,7 @@ def baseline(args) -> dict:
         pointwise_log_likelihood(ps, w["X"], w["Y"], lik, points=pts)
         posterior_predictive(ps, w["X"], lik, points=pts, random_seed=0)
 
-    out = _time({"matrices_to_host": matrices, "matrices_to_host_again": matrices}, args.reps)
+    out = _timing.by_statistic(_timing.time_legs(dict.fromkeys(LEGS, matrices), args.reps))
     pkg = os.path.dirname(os.path.abspath(pymc_bart_amd.__file__))
     out["package"] = os.path.relpath(pkg, HERE)
     out["has_loo_pit"] = hasattr(pymc_bart_amd, "loo_pit")
@@ -60,29 +58,18 @@ def baseline(args) -> dict:
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--draws", type=int, default=1000)
-    ap.add_argument("--tune", type=int, default=10)
-    ap.add_argument("--particles", type=int, default=10)
-    ap.add_argument("--small", action="store_true", help="a tenth of the rows (a quick look, not the record)")
-    ap.add_argument("--baseline-root", default=None, help="a built checkout of the parent commit: the baseline's package")
-    ap.add_argument("--baseline-leg", action="store_true", help=argparse.SUPPRESS)  # (the child process of --baseline-root)
-    ap.add_argument("--root", default=HERE, help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "psis_expect_timing.json"))
-    args = ap.parse_args(argv)
+    args = parser("psis_expect_timing.json").parse_args(argv)
     args.n = 100_000 // (10 if args.small else 1)
     os.environ.setdefault("PGB_JIT_CACHE", tempfile.mkdtemp(prefix="pgb_jit_timing_"))
     sys.path.insert(0, os.path.abspath(args.root))
     if args.baseline_leg:
-        print("BASELINE " + json.dumps(baseline(args)))
+        _timing.print_baseline(baseline(args))
         return 0
     import warnings
 
     import numpy as np
-    import torch
+    import torch  # noqa: F401
 
-    import occupancy_guard
     from pymc_bart_amd import loo_pit, pointwise_log_likelihood, posterior_predictive
     from pymc_bart_amd.loo import loo
     from pymc_bart_amd.sampler import default_backend
@@ -105,8 +92,8 @@ def main(argv=None) -> int:
 
     legs = {"loo_pit": leg_pit, "loo": leg_loo}
     if not args.baseline_root:
-        legs.update({"matrices_to_host": leg_matrices, "matrices_to_host_again": leg_matrices})
-    timed = _time(legs, args.reps)
+        legs.update(dict.fromkeys(LEGS, leg_matrices))
+    timed = _timing.by_statistic(_timing.time_legs(legs, args.reps))
     # (b) the kernels alone, on the two matrices of the same fit, resident
     if "ll" not in last:
         leg_matrices()
@@ -126,33 +113,19 @@ def main(argv=None) -> int:
         "k_psis_expect<0> (value)": lambda: lib.check(expect_call(mem.ptr(md), D, n, n, M, mem.ptr(gd), n, None, 0,
                                                                   mem.ptr(od), mem.stream_ptr), "pgb_psis_expect"),
     }
-    ev = {k: [] for k in kernels}
-    for rep in range(args.reps + 1):
-        for k, f in kernels.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            torch.cuda.synchronize()
-            if rep:
-                ev[k].append(a.elapsed_time(b))
-    kernel_ms = {k: round(float(np.median(v)), 3) for k, v in ev.items()}
+    kernel_ms = {k: round(v, 3) for k, v in _timing.events_ms(kernels, args.reps).items()}
     kernels["k_psis_expect<1> (PIT)"]()
     same = bool(np.array_equal(mem.to_host(od).reshape(4, n)[2], last["pit"]["loo_pit"]))
     del md, gd, od
     if args.baseline_root:
-        cmd = [sys.executable, os.path.abspath(__file__), "--baseline-leg", "--root", os.path.abspath(args.baseline_root),
-               "--reps", str(args.reps), "--draws", str(args.draws), "--tune", str(args.tune), "--particles",
-               str(args.particles)] + (["--small"] if args.small else [])
-        txt = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=900).stdout
-        base = json.loads([ln for ln in txt.splitlines() if ln.startswith("BASELINE ")][-1][9:])
+        base = _timing.run_baseline(__file__, args.baseline_root, baseline_argv(args))
         where = "a checkout of the parent commit, in a process of its own"
     else:
-        base = {k: {leg: v[leg] for leg in ("matrices_to_host", "matrices_to_host_again")} for k, v in timed.items()}
+        base = {k: {leg: v[leg] for leg in LEGS} for k, v in timed.items()}
         where = "this tree (its two matrix calls are the parent's)"
     bm = base["median_ms"]
     spread = abs(bm["matrices_to_host"] - bm["matrices_to_host_again"])
-    within = max(base["max_ms"][k] - base["min_ms"][k] for k in ("matrices_to_host", "matrices_to_host_again"))
+    within = max(base["max_ms"][k] - base["min_ms"][k] for k in LEGS)
     med = timed["median_ms"]
     r = last["pit"]
     line = {"metric": "ms_per_call", "reps": args.reps, "small": bool(args.small),
@@ -169,11 +142,8 @@ def main(argv=None) -> int:
             "loo_pit_result": {"elpd_loo": r["elpd_loo"], "n_high_k": r["n_high_k"], "n_clamped": r["n_clamped"],
                                "mean_loo_pit": float(r["loo_pit"].mean()), "n_capped": r["n_capped"],
                                "n_exhausted": r["n_exhausted"]},
-            "kernels": [k for k in occupancy_guard.table() if k["kernel"].startswith("k_psis")]}
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+            "kernels": _timing.kernel_rows("k_psis")}
+    _timing.write(args.out, line)
     return 0
 
 

@@ -25,14 +25,11 @@ results and the baseline's, and prints it as one JSON line.  Nothing is required
 
 from __future__ import annotations
 
-import argparse
-import ctypes as C
 import json
-import os
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
+from _timing import HERE
 
 SHAPES = {
     "plot": dict(n=1000, p=10, m=50, draws=200),
@@ -41,94 +38,46 @@ SHAPES = {
 GROUPS = 8
 
 
-def _fit(shape):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
-    from pymc_bart_amd.utils import _get_posterior_sampler
-    from pymc_bart_amd.workloads import cfg2
-
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
-    return w["X"], w["Y"], _get_posterior_sampler(op), time.perf_counter() - t0
-
-
-def _time(legs: dict, reps: int) -> dict:
-    import numpy as np
-    import torch
-
-    for f in legs.values():
-        f()
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return {k: {"median_ms": round(float(np.median(v)), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-            for k, v in ms.items()}
-
-
 def _kernel_alone(sampler, X, w, gid, reps):
     """``pgb_row_reduce`` (workspace cleared, ``k_rowreduce``, the wait for the stream) on the resident predictions of
     every draw at every row, by stream events."""
     import numpy as np
-    import torch
 
     from pymc_bart_amd import average
 
     job = average.AverageJob(sampler, X, None, w, gid)
-    be = job.hip_backend("the timing of pgb_row_reduce runs")
-    lib, mem = be.lib, be.mem
-    n, D, K, p = job.n, job.D, job.K, job.p
-    xd = mem.from_host(job.X)
-    md = mem.empty((D * K * n,), np.float64)
-    carr = job.pool.as_c()
-    lib.check(lib.lib.pgb_predict(C.byref(carr), job.fidx.ctypes.data, D, job.m, mem.ptr(xd), n, p, p, None, 0, mem.ptr(md),
-                                  mem.stream_ptr), "pgb_predict")
+    res = _timing.resident_predictions(job)
+    lib, mem = res.backend.lib, res.backend.mem
+    n, D, K = job.n, job.D, job.K
     wd, gd = mem.from_host(job.weights), mem.from_host(job.gid)
     ws = mem.empty((job.ws_bytes // 8,), np.float64)
     reduce_ = lib.rowreduce_entry_points()[0]
-    ev = []
-    for _ in range(reps + 1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        lib.check(reduce_(mem.ptr(md), None, D, K, n, n, mem.ptr(wd), mem.ptr(gd), None, None, None, None, job.G, job.code, 0, 1,
-                          mem.ptr(ws), None, mem.stream_ptr), "pgb_row_reduce")
-        b.record()
-        torch.cuda.synchronize()
-        ev.append(a.elapsed_time(b))
-    return float(np.median(ev[1:])), 8.0 * D * K * n
+    ms = _timing.events_ms(lambda: lib.check(reduce_(mem.ptr(res.pred), None, D, K, n, n, mem.ptr(wd), mem.ptr(gd), None, None,
+                                                     None, None, job.G, job.code, 0, 1, mem.ptr(ws), None, mem.stream_ptr),
+                                             "pgb_row_reduce"), reps)
+    return ms, 8.0 * D * K * n
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap = _timing.base_parser("rowreduce_timing.json", "plot,cfg2")
     ap.add_argument("--host-reps", type=int, default=2)
-    ap.add_argument("--shapes", default="plot,cfg2")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "rowreduce_timing.json"))
     args = ap.parse_args(argv)
     names = [s for s in args.shapes.split(",") if s]
     sys.path.insert(0, HERE)
-    sys.path.insert(0, os.path.join(HERE, "tools"))
     import numpy as np
     import torch  # noqa: F401
 
-    import occupancy_guard
     from pymc_bart_amd import average_contrast, average_prediction, bayes_r2
+    from pymc_bart_amd.utils import _get_posterior_sampler
 
-    line = {"metric": "ms_per_call", "reps": args.reps, "host_reps": args.host_reps, "groups": GROUPS, "shapes": {},
+    line = {"metric": "ms_per_call", "reps": args.reps, "host_reps": args.host_reps, "groups": GROUPS,
+            "shapes": _timing.kept_shapes(args.out, names),
             "baseline": "sample_posterior of all draws to the host (twice for the contrast) + NumPy, in this process: the "
                         "parent commit's sample_posterior is this tree's"}
-    if os.path.exists(args.out):
-        with open(args.out) as fh:
-            line["shapes"] = {k: v for k, v in json.load(fh).get("shapes", {}).items() if k not in names}
     for name in names:
         shape = SHAPES[name]
-        X, Y, sampler, secs = _fit(shape)
+        f = _timing.fit(shape)
+        X, Y, sampler, secs = f.X, f.Y, _get_posterior_sampler(f.op), f.seconds
         n, D = X.shape[0], sampler.n_draws
         rng = np.random.default_rng(3)
         w = rng.uniform(0.5, 1.5, n)
@@ -158,7 +107,7 @@ def main(argv=None) -> int:
         host_legs = {"average_prediction": lambda: host.__setitem__("average_prediction", (pull(X) @ ind) / W),
                      "average_contrast": lambda: host.__setitem__("average_contrast", ((pull(Xa) - pull(Xb)) @ ind) / W),
                      "bayes_r2": host_r2}
-        t_dev, t_host = _time(legs, args.reps), _time(host_legs, args.host_reps)
+        t_dev, t_host = _timing.time_legs(legs, args.reps), _timing.time_legs(host_legs, args.host_reps)
         k_ms, k_bytes = _kernel_alone(sampler, X, w, gid, args.reps)
         row = {"shape": dict(shape, chain_seconds=round(secs, 1)), "calls": {}}
         for key in legs:
@@ -171,12 +120,9 @@ def main(argv=None) -> int:
         row["pgb_row_reduce_read_GB_per_s"] = round(k_bytes / k_ms / 1e6, 1)
         print(f"[rowreduce_timing] {name}: {json.dumps(row)}", file=sys.stderr, flush=True)
         line["shapes"][name] = row
-        del X, Y, sampler, ind, dev, host
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_rowreduce")]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+        del X, Y, sampler, ind, dev, host, f
+    line["kernels"] = _timing.kernel_rows("k_rowreduce")
+    _timing.write(args.out, line)
     return 0
 
 

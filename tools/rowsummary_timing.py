@@ -24,15 +24,11 @@ per shape whether the new call is below the baseline by more than the baseline's
 
 from __future__ import annotations
 
-import argparse
-import ctypes as C
 import json
 import os
-import subprocess
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
 
 SHAPES = {
     "plot": dict(n=1000, p=10, m=50, draws=200),
@@ -40,38 +36,14 @@ SHAPES = {
 }
 QUANTILES = (0.03, 0.5, 0.97)
 HDI_PROB = 0.94
+LEGS = ("host", "host_again")
 
 
 def _fit(shape):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
     from pymc_bart_amd.utils import _get_posterior_sampler
-    from pymc_bart_amd.workloads import cfg2
 
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
-    return w["X"], _get_posterior_sampler(op), time.perf_counter() - t0
-
-
-def _time(legs: dict, reps: int) -> dict:
-    import numpy as np
-    import torch
-
-    for f in legs.values():
-        f()
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": {k: round(float(np.median(v)), 3) for k, v in ms.items()},
-            "min_ms": {k: round(min(v), 3) for k, v in ms.items()},
-            "max_ms": {k: round(max(v), 3) for k, v in ms.items()}}
+    f = _timing.fit(shape)
+    return f.X, _get_posterior_sampler(f.op), f.seconds
 
 
 def on_the_host(sampler, X):
@@ -98,7 +70,7 @@ def baseline(names, reps) -> dict:
     out = {"has_summary_module": os.path.exists(os.path.join(os.path.dirname(pymc_bart_amd.__file__), "summary.py"))}
     for name in names:
         X, sampler, secs = _fit(SHAPES[name])
-        out[name] = _time({"host": lambda: on_the_host(sampler, X), "host_again": lambda: on_the_host(sampler, X)}, reps)
+        out[name] = _timing.by_statistic(_timing.time_legs(dict.fromkeys(LEGS, lambda: on_the_host(sampler, X)), reps))
         out[name]["chain_seconds"] = round(secs, 1)
     return out
 
@@ -107,59 +79,36 @@ def _kernel_alone(sampler, X, reps):
     """``pgb_row_summary`` on the resident predictions of every draw at every row, by stream events; also whether its
     output is what ``posterior_summary`` returned."""
     import numpy as np
-    import torch
 
     from pymc_bart_amd import summary
 
     job = summary.SummaryJob(sampler, X, None, QUANTILES, HDI_PROB, "identity", None, None)
-    be = job.backend()
-    lib, mem = be.lib, be.mem
-    n, D, K, p = job.n, job.D, job.K, job.p
-    xd = mem.from_host(job.X)
-    md = mem.empty((D * K * n,), np.float64)
-    carr = job.pool.as_c()
-    lib.check(lib.lib.pgb_predict(C.byref(carr), job.fidx.ctypes.data, D, job.m, mem.ptr(xd), n, p, p, None, 0, mem.ptr(md),
-                                  mem.stream_ptr), "pgb_predict")
+    res = _timing.resident_predictions(job)
+    lib, mem = res.backend.lib, res.backend.mem
+    n, D, K = job.n, job.D, job.K
     rows = 2 + job.q.size + 2
     od = mem.empty((rows * K * n,), np.float64)
     call = lib.rowsummary_entry_point()
-    ev = []
-    for _ in range(reps + 1):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        lib.check(call(mem.ptr(md), D, K * n, K * n, None, job.code, job.q.ctypes.data, int(job.q.size), job.hdi_k,
-                       mem.ptr(od), mem.stream_ptr), "pgb_row_summary")
-        b.record()
-        torch.cuda.synchronize()
-        ev.append(a.elapsed_time(b))
-    return float(np.median(ev[1:])), mem.to_host(od).reshape(rows, K, n)
+    ms = _timing.events_ms(lambda: lib.check(call(mem.ptr(res.pred), D, K * n, K * n, None, job.code, job.q.ctypes.data,
+                                                  int(job.q.size), job.hdi_k, mem.ptr(od), mem.stream_ptr),
+                                             "pgb_row_summary"), reps)
+    return ms, mem.to_host(od).reshape(rows, K, n)
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="plot,large")
-    ap.add_argument("--baseline-root", default=None, help="a built checkout of the parent commit: the baseline's package")
-    ap.add_argument("--baseline-leg", action="store_true", help=argparse.SUPPRESS)  # (the child process of --baseline-root)
-    ap.add_argument("--root", default=HERE, help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "rowsummary_timing.json"))
-    args = ap.parse_args(argv)
+    args = _timing.base_parser("rowsummary_timing.json", "plot,large", baseline=True).parse_args(argv)
     names = [s for s in args.shapes.split(",") if s]
     sys.path.insert(0, os.path.abspath(args.root))
     if args.baseline_leg:
-        print("BASELINE " + json.dumps(baseline(names, args.reps)), flush=True)
+        _timing.print_baseline(baseline(names, args.reps))
         return 0
-    sys.path.insert(0, os.path.join(HERE, "tools"))
     import numpy as np
     import torch  # noqa: F401
 
-    import occupancy_guard
     from pymc_bart_amd import posterior_summary
 
-    line = {"metric": "ms_per_call", "reps": args.reps, "quantiles": list(QUANTILES), "hdi_prob": HDI_PROB, "shapes": {}}
-    if os.path.exists(args.out):
-        with open(args.out) as fh:
-            line["shapes"] = {k: v for k, v in json.load(fh).get("shapes", {}).items() if k not in names}
+    line = {"metric": "ms_per_call", "reps": args.reps, "quantiles": list(QUANTILES), "hdi_prob": HDI_PROB,
+            "shapes": _timing.kept_shapes(args.out, names)}
     new = {}
     for name in names:
         shape = SHAPES[name]
@@ -169,41 +118,33 @@ def main(argv=None) -> int:
         def leg():
             last["res"] = posterior_summary(sampler, X, quantiles=QUANTILES, hdi_prob=HDI_PROB)
 
-        t = _time({"posterior_summary": leg}, args.reps)
+        t = _timing.time_legs({"posterior_summary": leg}, args.reps)["posterior_summary"]
         k_ms, stats = _kernel_alone(sampler, X, args.reps)
         res = last["res"]
         same = bool(np.array_equal(stats[0].T, res["mean"]) and np.array_equal(np.moveaxis(stats[5:7], 1, 2), res["hdi"]))
-        new[name] = {"shape": dict(shape, chain_seconds=round(secs, 1)),
-                     "median_ms": t["median_ms"]["posterior_summary"], "min_ms": t["min_ms"]["posterior_summary"],
-                     "max_ms": t["max_ms"]["posterior_summary"], "k_rowsum_ms": round(k_ms, 4),
-                     "k_rowsum_share_of_the_call": round(k_ms / t["median_ms"]["posterior_summary"], 4),
+        new[name] = {"shape": dict(shape, chain_seconds=round(secs, 1)), **t, "k_rowsum_ms": round(k_ms, 4),
+                     "k_rowsum_share_of_the_call": round(k_ms / t["median_ms"], 4),
                      "k_rowsum_columns_per_s": round(X.shape[0] * sampler.n_outputs / k_ms * 1e3, 1),
                      "k_rowsum_equals_the_call_bits": same}
         print(f"[rowsummary_timing] {name}: {json.dumps(new[name])}", file=sys.stderr, flush=True)
         del X, sampler, stats, last
     base = None
     if args.baseline_root:
-        cmd = [sys.executable, os.path.abspath(__file__), "--baseline-leg", "--root", os.path.abspath(args.baseline_root),
-               "--reps", str(args.reps), "--shapes", ",".join(names)]
-        txt = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, text=True, timeout=1100).stdout
-        base = json.loads([ln for ln in txt.splitlines() if ln.startswith("BASELINE ")][-1][9:])
+        base = _timing.run_baseline(__file__, args.baseline_root, ["--reps", str(args.reps), "--shapes", ",".join(names)])
     for name in names:
         row = new[name]
         if base is not None:
             b = base[name]
             bm = b["median_ms"]
-            spread = max(abs(bm["host"] - bm["host_again"]), max(b["max_ms"][k] - b["min_ms"][k] for k in ("host", "host_again")))
+            spread = _timing.spread(b, LEGS)
             row["baseline"] = {"measured_on": "a checkout of the parent commit, in a process of its own",
                                "has_summary_module": base["has_summary_module"], **b}
             row["baseline_spread_ms"] = round(spread, 3)
             row["speedup"] = round(min(bm.values()) / row["median_ms"], 2)
             row["below_the_baseline_by_more_than_its_spread"] = bool(row["median_ms"] < min(bm.values()) - spread)
         line["shapes"][name] = row
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"] == "k_rowsum"]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+    line["kernels"] = _timing.kernel_rows(lambda k: k == "k_rowsum")
+    _timing.write(args.out, line)
     return 0
 
 

@@ -5,7 +5,7 @@
 * ``plot``  plot-sized: n = 1000, p = 10, m = 50, 100 stored draws, 20 of them attributed;
 * ``cfg2``  cfg2-shaped: 100 k x 50, m = 200, 50 stored draws, 8 of them attributed.
 
-Kernels alone (``PGB_WALK_TIMING``; ``pgb_shap_interactions_kernel_ms``, ``pgb_shap_kernel_ms``): the device buffers of
+Kernels alone (``_timing.walk_timing()``; ``pgb_shap_interactions_kernel_ms``, ``pgb_shap_kernel_ms``): the device buffers of
 ``device_blocks`` are timed block by block and never copied to the host, the kernel times of the blocks added up; at
 most ``--kernel-rows`` rows (default 16384), with every column and with the first 8.  The public calls run from host
 arrays to host results, after warming, median of ``--reps``: with every column at ``plot``; at ``cfg2`` with the first 8
@@ -19,16 +19,13 @@ Writes ``profiles/shap_interaction_timing.json`` (``--out``) and prints it as on
 
 from __future__ import annotations
 
-import argparse
 import ctypes as C
 import json
-import os
 import sys
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [HERE, os.path.join(HERE, "tools")]
-
-from shap_timing import SHAPES, _fit, _time  # noqa: E402
+import _timing
+from _timing import HERE
+from shap_timing import SHAPES
 
 
 def _kernels_alone(s, X, picks, cols, reps):
@@ -56,40 +53,34 @@ def _kernels_alone(s, X, picks, cols, reps):
         return acc
 
     a, b = [], []
-    os.environ["PGB_WALK_TIMING"] = "1"
-    try:
+    with _timing.walk_timing():
         for _ in range(reps + 1):
             a.append(total(shap_interaction.device_blocks(be, pool, table, m, K, Xc, cc, pk), x_ms))
             b.append(total(shap.device_blocks(be, pool, table, m, K, Xc, pk), s_ms))
-    finally:
-        del os.environ["PGB_WALK_TIMING"]
     kx, ks = float(np.median(a[1:])), float(np.median(b[1:]))
     return {"rows": int(Xc.shape[0]), "cols": int(cc.size), "k_shap_interaction_ms": round(kx, 4), "k_shap_ms": round(ks, 4),
             "k_shap_interaction_over_k_shap": round(kx / ks, 1)}
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="plot,cfg2")
+    ap = _timing.base_parser("shap_interaction_timing.json", "plot,cfg2")
     ap.add_argument("--kernel-rows", type=int, default=16384)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "shap_interaction_timing.json"))
     args = ap.parse_args(argv)
+    sys.path.insert(0, HERE)
     import numpy as np
     import torch  # noqa: F401
 
-    import occupancy_guard
     from pymc_bart_amd import shap_interaction_summary, shap_interaction_values, shap_values
     from pymc_bart_amd.utils import _get_posterior_sampler
 
     line = {"metric": "ms_per_call", "reps": args.reps, "shapes": {}}
     for name in [s for s in args.shapes.split(",") if s]:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        s = _get_posterior_sampler(op)
+        f = _timing.fit(shape)
+        X, s, secs = f.X, _get_posterior_sampler(f.op), f.seconds
         picks = np.random.default_rng(3).integers(0, s.n_draws, size=shape["picks"]).tolist()
         cols = None if name == "plot" else list(range(8))
-        t = _time({"shap_interaction_values": lambda: shap_interaction_values(s, X, cols=cols, draws=picks),
+        t = _timing.time_legs({"shap_interaction_values": lambda: shap_interaction_values(s, X, cols=cols, draws=picks),
                    "shap_interaction_summary": lambda: shap_interaction_summary(s, X, cols=cols, draws=picks),
                    "shap_values": lambda: shap_values(s, X, draws=picks)}, args.reps)
         Xk = X[:args.kernel_rows]
@@ -100,12 +91,9 @@ def main(argv=None) -> int:
         row["row_sum_max_abs_gap"] = float(np.max(np.abs(vals["values"].sum(-1) - ref["values"])))
         line["shapes"][name] = row
         print(f"[shap_interaction_timing] {name}: {json.dumps(row)}", file=sys.stderr, flush=True)
-        del X, op, s
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_shap_interaction<")]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+        del X, f, s
+    line["kernels"] = _timing.kernel_rows("k_shap_interaction<")
+    _timing.write(args.out, line)
     return 0
 
 

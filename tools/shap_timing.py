@@ -7,7 +7,7 @@ The public call is timed from host arrays to host results, after warming, median
 * ``plot``  plot-sized: n = 1000, p = 10, m = 50, 100 stored draws, 20 of them attributed;
 * ``cfg2``  cfg2-shaped: 100 k x 50, m = 200, 50 stored draws, 8 of them attributed.
 
-Also recorded, per shape: ``k_shap`` alone between stream events (``PGB_WALK_TIMING``, ``pgb_shap_kernel_ms``) and
+Also recorded, per shape: ``k_shap`` alone between stream events (``_timing.walk_timing()``, ``pgb_shap_kernel_ms``) and
 ``k_predict`` alone (``pgb_walk_kernel_ms``), their ratio, ``shap_summary`` (the attributions stay on the device), and
 the kernels' resource rows.  There is no earlier implementation of the attributions: no speed-up is claimed, the ratio
 to ``pgb_predict`` says what an attribution costs next to a prediction.
@@ -19,49 +19,17 @@ Writes ``profiles/shap_timing.json`` (``--out``) and prints it as one JSON line.
 
 from __future__ import annotations
 
-import argparse
 import ctypes as C
 import json
-import os
 import sys
-import time
 
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _timing
+from _timing import HERE
 
 SHAPES = {
     "plot": dict(n=1000, p=10, m=50, draws=100, picks=20),
     "cfg2": dict(n=100_000, p=50, m=200, draws=50, picks=8),
 }
-
-
-def _fit(shape):
-    from pymc_bart_amd import BARTOp
-    from pymc_bart_amd.chains import sample_chain
-    from pymc_bart_amd.workloads import cfg2
-
-    w = cfg2(n=shape["n"], p=shape["p"], m=shape["m"])
-    op = BARTOp(w["X"], w["Y"], m=w["m"])
-    t0 = time.perf_counter()
-    sample_chain(op, 10, shape["draws"], num_particles=10, random_seed=7, keep_draws=False)
-    return w["X"], op, time.perf_counter() - t0
-
-
-def _time(legs: dict, reps: int) -> dict:
-    import numpy as np
-    import torch
-
-    for f in legs.values():
-        f()
-    ms = {k: [] for k in legs}
-    for _ in range(reps):
-        for k, f in legs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            f()
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return {k: {"median_ms": round(float(np.median(v)), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
-            for k, v in ms.items()}
 
 
 def _kernels_alone(s, rows, picks, reps):
@@ -72,8 +40,7 @@ def _kernels_alone(s, rows, picks, reps):
     shap_ms, walk_ms = lib.lib.pgb_shap_kernel_ms, lib.lib.pgb_walk_kernel_ms
     shap_ms.argtypes = walk_ms.argtypes = [C.POINTER(C.c_double)]
     a, b = [], []
-    os.environ["PGB_WALK_TIMING"] = "1"
-    try:
+    with _timing.walk_timing():
         for _ in range(reps + 1):
             v = C.c_double(-1.0)
             s.shap(rows, picks)
@@ -83,33 +50,26 @@ def _kernels_alone(s, rows, picks, reps):
             s.sample_posterior(rows, picks, None)
             walk_ms(C.byref(v))
             b.append(v.value)
-    finally:
-        del os.environ["PGB_WALK_TIMING"]
     ks, kp = float(np.median(a[1:])), float(np.median(b[1:]))
     return {"k_shap_ms": round(ks, 4), "k_predict_ms": round(kp, 4), "k_shap_over_k_predict": round(ks / kp, 1)}
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="plot,cfg2")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "shap_timing.json"))
-    args = ap.parse_args(argv)
-    sys.path[:0] = [HERE, os.path.join(HERE, "tools")]
+    args = _timing.base_parser("shap_timing.json", "plot,cfg2").parse_args(argv)
+    sys.path.insert(0, HERE)
     import numpy as np
     import torch  # noqa: F401
 
-    import occupancy_guard
     from pymc_bart_amd import shap_summary, shap_values
     from pymc_bart_amd.utils import _get_posterior_sampler
 
     line = {"metric": "ms_per_call", "reps": args.reps, "shapes": {}}
     for name in [s for s in args.shapes.split(",") if s]:
         shape = SHAPES[name]
-        X, op, secs = _fit(shape)
-        s = _get_posterior_sampler(op)
+        f = _timing.fit(shape)
+        X, s, secs = f.X, _get_posterior_sampler(f.op), f.seconds
         picks = np.random.default_rng(3).integers(0, s.n_draws, size=shape["picks"]).tolist()
-        t = _time({"shap_values": lambda: shap_values(s, X, draws=picks),
+        t = _timing.time_legs({"shap_values": lambda: shap_values(s, X, draws=picks),
                    "shap_summary": lambda: shap_summary(s, X, draws=picks),
                    "sample_posterior": lambda: s.sample_posterior(X, picks, None)}, args.reps)
         row = {"shape": dict(shape, chain_seconds=round(secs, 1)), **t,
@@ -120,12 +80,9 @@ def main(argv=None) -> int:
         row["efficiency_max_abs_gap"] = float(np.max(np.abs(vals["base"][:, None] + vals["values"].sum(-1) - pred)))
         line["shapes"][name] = row
         print(f"[shap_timing] {name}: {json.dumps(row)}", file=sys.stderr, flush=True)
-        del X, op, s
-    line["kernels"] = [k for k in occupancy_guard.table() if k["kernel"].startswith("k_shap<")]
-    with open(args.out, "w") as fh:
-        json.dump(line, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps(line))
+        del X, f, s
+    line["kernels"] = _timing.kernel_rows("k_shap<")
+    _timing.write(args.out, line)
     return 0
 
 

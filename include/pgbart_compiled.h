@@ -21,6 +21,13 @@
  * the host and the device) and explicit comparisons, no libm.  Both compiles run with -ffp-contract=off.
  * The result goes through the contract's clamp ([-2047, 2047], NaN -> -2047) and the fixed-point sums of the
  * callback family: on a given backend the compiled family and the callback family are the same sampler.
+ *
+ * A likelihood may carry a second body, its SAMPLER BODY: the inside of
+ *     double r(double mu, double aux, const double <param 0>, ..., const double <param n-1>)
+ * (mu[0 .. K-1] for K outputs; no y), which returns one replicated observation.  It is compiled into a code object of
+ * its own (mark 2: the kernel k_ppc_compiled of csrc/k_ppc_compiled.hip, launched by pgb_ppc_draw_compiled) and into a
+ * host evaluator.  It calls the vocabulary above plus the RANDOM vocabulary (section "vocabulary" below), whose
+ * numeric contract -- the samplers, the addressing of every call, the caps -- is include/pgbart_ppc.h.
  */
 #ifndef PGBART_COMPILED_H
 #define PGBART_COMPILED_H
@@ -45,8 +52,14 @@ typedef struct {
   int64_t sizeof_dev, sizeof_job, sizeof_cmd, sizeof_ctrl, sizeof_acc;
   uint64_t headers_hash;  /* PGB_HEADERS_HASH: a hash of the kernel headers (pymc_bart_amd/compiled.py) */
   int32_t linear_leaves;  /* 0: the constant-leaf pass, 1: the linear-leaf pass (response linear / mix) */
-  int32_t pointwise;      /* 0: a sampler's pass kernel; 1: k_pointwise_compiled (pgbart_pointwise.h), no pass kernel */
+  int32_t pointwise;      /* the object's MARK.  0: a sampler's pass kernel; 1: k_pointwise_compiled
+                             (pgbart_pointwise.h), no pass kernel; 2: k_ppc_compiled, the SAMPLER BODY of the likelihood
+                             (pgbart_ppc.h), no pass kernel, n_outputs is the K of the sampler body's mu */
 } pgb_compiled_layout;
+#define PGB_COMPILED_MARK_PASS 0
+#define PGB_COMPILED_MARK_POINTWISE 1
+#define PGB_COMPILED_MARK_SAMPLER 2
+#define PGB_PPC_COMPILED_KERNEL "k_ppc_compiled"
 
 /* The params of one launch, by value (they arrive in SGPRs with the kernel arguments). */
 typedef struct {
@@ -91,7 +104,15 @@ int pgb_compiled_probe(pgb_handle* h, const double* y, const double* mu, const d
  *   log_ndtr         pgb_lphi_t                       (log Phi, the probit family's function)
  *   softplus         pgb_softplus_t                   (log(1 + e^x))
  *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour)
- *   lgamma           pgb_cl_lgamma                    (log Gamma(x), x > 0: + - * / and pgb_log_t only) */
+ *   lgamma           pgb_cl_lgamma                    (log Gamma(x), x > 0: + - * / and pgb_log_t only)
+ * A unit that compiles a SAMPLER BODY also defines PGB_COMPILED_SAMPLER_VOCABULARY, after it has included
+ * pgbart_ppc.h, and has a `pgb_ppc_ctx* pgb_cl_rng` in scope around the body: the random vocabulary is on as well --
+ *   uniform()        pgb_ppc_ctx_uniform       [0, 1)     uniform_open()   pgb_ppc_ctx_uniform_open   (0, 1)
+ *   normal()         pgb_ppc_ctx_normal                   gamma(a)         pgb_ppc_ctx_gamma
+ *   poisson(lam)     pgb_ppc_ctx_poisson
+ *   sqrt(x)          pgb_psis_sqrt                        floor(x)         pgb_ppc_floor
+ * -- with the addressing of repeated calls, the call cap and the flags as include/pgbart_ppc.h states them.  A
+ * density body never sees these names: a param of a density-only likelihood may be called gamma. */
 #if defined(PGB_COMPILED_VOCABULARY) && !defined(PGB_COMPILED_VOCABULARY_ON)
 #define PGB_COMPILED_VOCABULARY_ON
 #ifndef PGB_COMPILED_VOCABULARY_FNS
@@ -139,6 +160,15 @@ PGB_HD double pgb_cl_lgamma(double x, const double* logt) {
 #define fmin(a, b) pgb_cl_fmin((double)(a), (double)(b))
 #define fmax(a, b) pgb_cl_fmax((double)(a), (double)(b))
 #define lgamma(x) pgb_cl_lgamma((double)(x), PGB_CL_LOGT)
+#ifdef PGB_COMPILED_SAMPLER_VOCABULARY
+#define uniform() pgb_ppc_ctx_uniform(pgb_cl_rng)
+#define uniform_open() pgb_ppc_ctx_uniform_open(pgb_cl_rng)
+#define normal() pgb_ppc_ctx_normal(pgb_cl_rng)
+#define gamma(a) pgb_ppc_ctx_gamma(pgb_cl_rng, (double)(a))
+#define poisson(lam) pgb_ppc_ctx_poisson(pgb_cl_rng, (double)(lam))
+#define sqrt(x) pgb_psis_sqrt((double)(x), pgb_cl_rng->tb)
+#define floor(x) pgb_ppc_floor((double)(x))
+#endif
 #endif
 #if defined(PGB_COMPILED_VOCABULARY_END) && defined(PGB_COMPILED_VOCABULARY_ON)
 #undef PGB_COMPILED_VOCABULARY_ON
@@ -152,4 +182,14 @@ PGB_HD double pgb_cl_lgamma(double x, const double* logt) {
 #undef fmin
 #undef fmax
 #undef lgamma
+#ifdef PGB_COMPILED_SAMPLER_VOCABULARY
+#undef PGB_COMPILED_SAMPLER_VOCABULARY
+#undef uniform
+#undef uniform_open
+#undef normal
+#undef gamma
+#undef poisson
+#undef sqrt
+#undef floor
+#endif
 #endif

@@ -48,7 +48,33 @@
  * +-1.7976931348623157e308 (a NaN: 0.0) and sets PGB_PPC_CAPPED.  Flags are counted by every caller -- reported,
  * never silent, like n_clamped.
  *
- * The compiled and callback families have a log density only, no sampler: they are refused by name.
+ * SAMPLER BODIES (pgb_ppc_draw_compiled, below; the vocabulary is include/pgbart_compiled.h's).  A compiled
+ * likelihood may carry a second C body, the inside of
+ *     double r(double mu (or mu[0 .. K-1], K readable), double aux, const double <param>...)
+ * which returns ONE replicated observation -- there is no y.  It calls the density vocabulary and, in sampler bodies
+ * only, the random vocabulary:
+ *   uniform()       pgb_u01 of a pair's first half, in [0, 1)
+ *   uniform_open()  the open form of the same bits, in (0, 1)
+ *   normal()        the first normal of pgb_normal2 of one pair
+ *   gamma(a)        pgb_ppc_gamma       poisson(lam)    pgb_ppc_poisson
+ *   sqrt(x)         pgb_psis_sqrt       floor(x)        pgb_ppc_floor       (the helpers the built-in samplers use)
+ * The addressing rule above stands.  A body may call a random function more than once: the c-th call (c = 0, 1, ..
+ * in execution order) of one KIND within one evaluation uses that kind's purpose(s) plus PGB_PPC_CALL_STRIDE c in the
+ * purpose half of counter word 3.  The kinds: normal (purpose 16), uniform (17; uniform and uniform_open share the
+ * counter), gamma (18 .. 20), poisson (21, 22).  The purposes 16 .. 22 stay distinct mod 32 and never meet the
+ * sampler's 1 .. 6.  The offset is the `salt` of pgb_ppc_addr, added inside pgb_ppc_block; it is 0 for every built-in
+ * family and for c = 0, so that a body which restates a built-in family's formula reproduces pgb_ppc_value of that
+ * family bit for bit.  At most PGB_PPC_MAX_CALLS calls per kind per evaluation: beyond, a call draws nothing, returns
+ * a fixed value -- normal 0.0, uniform and uniform_open 0.5, gamma(a) a, poisson(lam) floor(lam) -- and sets
+ * PGB_PPC_EXHAUSTED.  ("Execution order" is C's: two calls of one kind inside ONE expression, normal() - normal(),
+ * are unsequenced, and two compilers may number them differently -- the values are as good, but a body that must give
+ * the same bits on the host and on the device puts such calls into statements of their own.)  A result that is not finite is capped and counted as PGB_PPC_CAPPED exactly as above.  The body
+ * owns its domain: its params are finite, nothing else is checked.  Host and device compile the body from the one text
+ * with -ffp-contract=off and no libm; the call counters and the flags live in a pgb_ppc_ctx the vocabulary macros
+ * reach as pgb_cl_rng.
+ *
+ * A compiled likelihood without a sampler body, and the callback family, have a log density only, no sampler: they are
+ * refused by name.
  */
 #ifndef PGBART_PPC_H
 #define PGBART_PPC_H
@@ -77,11 +103,14 @@
 #define PGB_PPC_RNG_POISSON_PTRS 22u /* PTRS, attempt t: (U, V)                                   */
 #define PGB_PPC_RNG_FIRST 16u
 #define PGB_PPC_RNG_LAST 22u
+#define PGB_PPC_CALL_STRIDE 32u /* sampler bodies: the c-th call of a kind adds 32 c to its purposes */
+#define PGB_PPC_MAX_CALLS 1024u /* ... and a kind has at most this many calls per evaluation (22 + 32 * 1023 < 2^16) */
 
 typedef struct {
   uint32_t k0, k1; /* seed */
   uint32_t c0, c1; /* global row */
   uint32_t c2;     /* position of the draw */
+  uint32_t salt;   /* added to every purpose: 0 but for the repeated calls of a sampler body */
 } pgb_ppc_addr;
 
 PGB_HD pgb_ppc_addr pgb_ppc_address(uint64_t seed, uint32_t draw_pos, uint64_t global_row) {
@@ -91,10 +120,11 @@ PGB_HD pgb_ppc_addr pgb_ppc_address(uint64_t seed, uint32_t draw_pos, uint64_t g
   a.c0 = (uint32_t)global_row;
   a.c1 = (uint32_t)(global_row >> 32);
   a.c2 = draw_pos;
+  a.salt = 0u;
   return a;
 }
 PGB_HD pgb_u32x4 pgb_ppc_block(const pgb_ppc_addr* a, uint32_t purpose, uint32_t attempt) {
-  return pgb_philox4x32_10(a->k0, a->k1, a->c0, a->c1, a->c2, (purpose << 16) | (attempt & 0xFFFFu));
+  return pgb_philox4x32_10(a->k0, a->k1, a->c0, a->c1, a->c2, ((purpose + a->salt) << 16) | (attempt & 0xFFFFu));
 }
 /* the pair in [0, 1) */
 PGB_HD pgb_u2 pgb_ppc_pair(const pgb_ppc_addr* a, uint32_t purpose, uint32_t attempt) {
@@ -201,6 +231,15 @@ PGB_HD double pgb_ppc_poisson(double lam, const pgb_ppc_addr* ad, const pgb_llta
   return pgb_ppc_floor(lam);
 }
 
+/* a value that is not finite: +-DBL_MAX (a NaN: 0.0), counted */
+PGB_HD double pgb_ppc_cap(double v, uint32_t* flags) {
+  if (!(v - v == 0.0)) {
+    *flags |= PGB_PPC_CAPPED;
+    v = v > 0.0 ? PGB_PPC_DBL_MAX : (v < 0.0 ? -PGB_PPC_DBL_MAX : 0.0);
+  }
+  return v;
+}
+
 /* One replicated observation.  mu: the K predictors (the offset included), finite; q: the draw's prepared row
  * (pgb_logpdf_prepare returned 0); flags: PGB_PPC_CAPPED / PGB_PPC_EXHAUSTED are OR-ed in.  A family without a sampler
  * gives 0.0 (the callers refuse it before). */
@@ -257,11 +296,65 @@ PGB_HD double pgb_ppc_value(int family, int K, const double* mu, const double* q
   } else {
     return 0.0;
   }
-  if (!(v - v == 0.0)) {
-    *flags |= PGB_PPC_CAPPED;
-    v = v > 0.0 ? PGB_PPC_DBL_MAX : (v < 0.0 ? -PGB_PPC_DBL_MAX : 0.0);
-  }
+  return pgb_ppc_cap(v, flags);
+}
+
+/* ---- sampler bodies: the state of ONE evaluation (the address, the tables, the flags, the calls so far of each kind)
+ * and the random vocabulary on it.  The unit that compiles a body calls pgb_ppc_ctx_begin, the body, pgb_ppc_ctx_end. */
+typedef struct {
+  pgb_ppc_addr ad;
+  const pgb_lltabs* tb;
+  uint32_t flags;
+  uint32_t n_normal, n_uniform, n_gamma, n_poisson;
+} pgb_ppc_ctx;
+
+PGB_HD void pgb_ppc_ctx_begin(pgb_ppc_ctx* c, uint64_t seed, uint32_t draw_pos, uint64_t global_row, const pgb_lltabs* tb) {
+  c->ad = pgb_ppc_address(seed, draw_pos, global_row);
+  c->tb = tb;
+  c->flags = 0u;
+  c->n_normal = c->n_uniform = c->n_gamma = c->n_poisson = 0u;
+}
+/* the body's value, capped; the evaluation's flags are OR-ed into *flags */
+PGB_HD double pgb_ppc_ctx_end(pgb_ppc_ctx* c, double v, uint32_t* flags) {
+  v = pgb_ppc_cap(v, &c->flags);
+  *flags |= c->flags;
   return v;
+}
+/* the address of the next call of a kind; 0 (and EXHAUSTED) past the cap */
+PGB_HD int pgb_ppc_ctx_next(pgb_ppc_ctx* c, uint32_t* calls, pgb_ppc_addr* a) {
+  if (*calls >= PGB_PPC_MAX_CALLS) {
+    c->flags |= PGB_PPC_EXHAUSTED;
+    return 0;
+  }
+  *a = c->ad;
+  a->salt = PGB_PPC_CALL_STRIDE * *calls;
+  *calls = *calls + 1u;
+  return 1;
+}
+PGB_HD double pgb_ppc_ctx_normal(pgb_ppc_ctx* c) {
+  pgb_ppc_addr a;
+  if (!pgb_ppc_ctx_next(c, &c->n_normal, &a)) return 0.0;
+  return pgb_ppc_normal(&a, PGB_PPC_RNG_NORMAL, 0u);
+}
+PGB_HD double pgb_ppc_ctx_uniform(pgb_ppc_ctx* c) {
+  pgb_ppc_addr a;
+  if (!pgb_ppc_ctx_next(c, &c->n_uniform, &a)) return 0.5;
+  return pgb_ppc_pair(&a, PGB_PPC_RNG_UNIFORM, 0u).u0;
+}
+PGB_HD double pgb_ppc_ctx_uniform_open(pgb_ppc_ctx* c) {
+  pgb_ppc_addr a;
+  if (!pgb_ppc_ctx_next(c, &c->n_uniform, &a)) return 0.5;
+  return pgb_ppc_pair_open(&a, PGB_PPC_RNG_UNIFORM, 0u).u0;
+}
+PGB_HD double pgb_ppc_ctx_gamma(pgb_ppc_ctx* c, double shape) {
+  pgb_ppc_addr a;
+  if (!pgb_ppc_ctx_next(c, &c->n_gamma, &a)) return shape;
+  return pgb_ppc_gamma(shape, &a, c->tb, &c->flags);
+}
+PGB_HD double pgb_ppc_ctx_poisson(pgb_ppc_ctx* c, double lam) {
+  pgb_ppc_addr a;
+  if (!pgb_ppc_ctx_next(c, &c->n_poisson, &a)) return pgb_ppc_floor(lam);
+  return pgb_ppc_poisson(lam, &a, c->tb, &c->flags);
 }
 
 /* the mid-p comparison of the PIT counts: pit = (#below + 0.5 #equal) / D */
@@ -276,6 +369,16 @@ typedef struct {
   const double* params_host; /* [D][n_params], host memory (NULL when n_params = 0) */
   const double* offset_dev;  /* [K][ld] added to the predictors, or NULL */
 } pgb_ppc_lik;
+
+/* A compiled likelihood's sampler body for pgb_ppc_draw_compiled. */
+typedef struct {
+  const void* code_object;   /* a gfx950 code object built as a sampler object: k_ppc_compiled, layout mark 2 */
+  int64_t code_bytes;
+  int32_t n_params;          /* params per draw: what the body declares */
+  const double* params_host; /* [D][n_params], host memory, finite (NULL when n_params = 0) */
+  const double* offset_dev;  /* [K][ld] added to the predictors, or NULL */
+  const double* aux_dev;     /* [n_rows] the body's aux column, or NULL (aux = 0.0) */
+} pgb_ppc_code;
 
 #ifdef __cplusplus
 extern "C" {
@@ -297,6 +400,16 @@ extern "C" {
 int pgb_ppc_draw(const double* mu_dev, int32_t D, int32_t K, int64_t n_rows, int64_t ld, int64_t row0,
                  const pgb_ppc_lik* lik, uint64_t seed, double* out_dev, int64_t ld_out, const double* y_dev,
                  int32_t* pit_counts_dev, int64_t* flags_host, void* stream);
+/* The same call with the sampler body of a compiled likelihood at the evaluation site (HIP library only, both particle
+ * builds; not part of pgbart.h): every argument rule of pgb_ppc_draw, and element (d, i) is the body's value at the
+ * predictors mu[d][.][i] + offset[.][i], aux[i] and the params of draw d, under the addressing of SAMPLER BODIES above.
+ * The code object is loaded per call and checked before any launch, each message naming both sides: the ELF header,
+ * the kernel, the layout record's magic, its mark (2: a pass-kernel or pointwise object is refused), the headers hash,
+ * n_params, the body's outputs against K, finite params.  pgb_ppc_draw keeps refusing the compiled family;
+ * pgb_pointwise_loglik and pgb_set_loglik_code refuse a sampler object. */
+int pgb_ppc_draw_compiled(const double* mu_dev, int32_t D, int32_t K, int64_t n_rows, int64_t ld, int64_t row0,
+                          const pgb_ppc_code* code, uint64_t seed, double* out_dev, int64_t ld_out, const double* y_dev,
+                          int32_t* pit_counts_dev, int64_t* flags_host, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,19 @@ class PpcLik(C.Structure):
     ]
 
 
+class PpcCode(C.Structure):
+    """``pgb_ppc_code`` (include/pgbart_ppc.h): a compiled likelihood's sampler body for ``pgb_ppc_draw_compiled``."""
+
+    _fields_ = [
+        ("code_object", C.c_void_p),
+        ("code_bytes", C.c_int64),
+        ("n_params", C.c_int32),
+        ("params_host", C.c_void_p),
+        ("offset_dev", C.c_void_p),
+        ("aux_dev", C.c_void_p),
+    ]
+
+
 #: ``pgb_loglik_fn``: int fn(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out)
 LOGLIK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                         C.c_int64, C.POINTER(C.c_double))
@@ -376,6 +389,18 @@ class PGBLibrary:
         """``pgb_ppc_draw`` (include/pgbart_ppc.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_ppc_draw
         f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(PpcLik), C.c_uint64,
+                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def ppc_compiled_entry_point(self):
+        """``pgb_ppc_draw_compiled`` (include/pgbart_ppc.h): HIP library only, hence not in SYMBOLS.  A library without
+        the symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_ppc_draw_compiled
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_ppc_draw_compiled (HIP library only)") from None
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(PpcCode), C.c_uint64,
                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
         f.restype = C.c_int
         return f

@@ -17,7 +17,9 @@ evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is
 code object holds the library's linear-leaf pass instead (``response="linear"`` / ``"mix"``, one output or K): one pass
 kernel per code object, and HIP only -- the CPU backends' callback family has constant leaves.  With ``pointwise=True``
 the code object holds no pass kernel but ``k_pointwise_compiled`` (``csrc/k_pointwise_compiled.hip``): the body inside
-the posterior tree walk, for scoring a fit (:mod:`pymc_bart_amd.pointwise`).  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
+the posterior tree walk, for scoring a fit (:mod:`pymc_bart_amd.pointwise`).  A likelihood may also carry a SAMPLER body -- how to draw one observation --
+which :func:`compile_sampler` turns into a third kind of code object, ``k_ppc_compiled`` (``csrc/k_ppc_compiled.hip``),
+and a host evaluator (:mod:`pymc_bart_amd.predictive`).  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
 everything that goes into them.
 """
 
@@ -42,6 +44,8 @@ INCLUDE = os.path.join(ROOT, "include")
 TU = os.path.join(CSRC, "k_loglik_compiled.hip")
 #: the unit of a POINTWISE code object (``compile_loglik(..., pointwise=True)``; include/pgbart_pointwise.h)
 TU_POINTWISE = os.path.join(CSRC, "k_pointwise_compiled.hip")
+#: the unit of a SAMPLER code object (``compile_sampler``; include/pgbart_ppc.h)
+TU_SAMPLER = os.path.join(CSRC, "k_ppc_compiled.hip")
 LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 #: the library's device flags (``__graft_entry__.HIPCC_FLAGS`` without ``-fPIC`` / ``-shared``; a test holds them equal)
@@ -69,6 +73,16 @@ VOCABULARY = {
     "fmax": "fmax(a, b): a > b ? a : b",
     "lgamma": "lgamma(x): log Gamma(x) for x > 0 (NaN otherwise), on the log table",
 }
+#: what a SAMPLER body may call on top of it (include/pgbart_ppc.h, "SAMPLER BODIES"); never a density body
+RANDOM_VOCABULARY = {
+    "uniform": "uniform(): a uniform in [0, 1)",
+    "uniform_open": "uniform_open(): a uniform in (0, 1), for a logarithm",
+    "normal": "normal(): a standard normal",
+    "gamma": "gamma(a): Gamma(a, 1), Marsaglia-Tsang (pgb_ppc_gamma)",
+    "poisson": "poisson(lam): Poisson(lam), inversion below 10 and PTRS from there (pgb_ppc_poisson)",
+    "sqrt": "sqrt(x): pgb_psis_sqrt",
+    "floor": "floor(x): pgb_ppc_floor",
+}
 _EXPLOG = ("exp", "log", "softplus", "lgamma")
 _C_KEYWORDS = {
     "auto", "break", "case", "char", "const", "continue", "default", "do", "double", "else", "enum", "extern",
@@ -90,8 +104,9 @@ class CompileError(RuntimeError):
     """A body the compilers refuse (or one that calls a function outside the vocabulary)."""
 
 
-def vocabulary_text() -> str:
-    return "; ".join(VOCABULARY.values()) + "; plus + - * /, comparisons, ?:, if, local double / int variables"
+def vocabulary_text(sampler: bool = False) -> str:
+    words = list(VOCABULARY.values()) + (list(RANDOM_VOCABULARY.values()) if sampler else [])
+    return "; ".join(words) + "; plus + - * /, comparisons, ?:, if, local double / int variables"
 
 
 # ---------------------------------------------------------------------------------------------------- validation
@@ -106,10 +121,14 @@ def check_outputs(n_outputs) -> int:
     return int(n_outputs)
 
 
-def validate(body: str, param_names, n_outputs: int = 1) -> tuple[str, ...]:
-    """Refuse, before any compiler runs, what the body may not contain.  Returns the param names as a tuple."""
+def validate(body: str, param_names, n_outputs: int = 1, sampler: bool = False) -> tuple[str, ...]:
+    """Refuse, before any compiler runs, what the body may not contain.  Returns the param names as a tuple.
+    ``sampler``: the body is a SAMPLER body -- it may call the random vocabulary too, has no ``y``, and no param may
+    carry a name of the random vocabulary."""
+    what = "sampler" if sampler else "likelihood"
+    vocabulary = {**VOCABULARY, **RANDOM_VOCABULARY} if sampler else VOCABULARY
     if not isinstance(body, str) or not body.strip():
-        raise ValueError("the body must be a non-empty string of C statements")
+        raise ValueError(f"the {'sampler ' if sampler else ''}body must be a non-empty string of C statements")
     K = check_outputs(n_outputs)
     names = tuple(param_names)
     if len(names) > MAX_PARAMS:
@@ -122,8 +141,10 @@ def validate(body: str, param_names, n_outputs: int = 1) -> tuple[str, ...]:
             raise ValueError(f"param name {nm!r} clashes with the body's arguments y, mu, aux")
         if K > 1 and nm == "K":
             raise ValueError("param name 'K' is reserved: a body of n_outputs >= 2 reads its number of outputs as K")
-        if nm in VOCABULARY:
-            raise ValueError(f"param name {nm!r} clashes with the vocabulary ({', '.join(VOCABULARY)})")
+        if nm in vocabulary:
+            raise ValueError(f"param name {nm!r} clashes with the vocabulary ({', '.join(vocabulary)})"
+                             + (": a likelihood with a sampler body reserves the random vocabulary's names"
+                                if nm in RANDOM_VOCABULARY else ""))
         if nm in _C_KEYWORDS:
             raise ValueError(f"param name {nm!r} is a C keyword")
         if nm.startswith("__") or nm.lower().startswith("pgb_"):
@@ -133,29 +154,33 @@ def validate(body: str, param_names, n_outputs: int = 1) -> tuple[str, ...]:
         seen.add(nm)
     for lineno, line in enumerate(body.splitlines(), 1):
         if line.lstrip().startswith("#") or line.lstrip().startswith("%:"):
-            raise ValueError(f"line {lineno}: preprocessor lines are not allowed in a likelihood body: {line.strip()!r}")
+            raise ValueError(f"line {lineno}: preprocessor lines are not allowed in a {what} body: {line.strip()!r}")
     # (on the raw text: no line splice can move code into or out of a comment)
-    for bad, what in (("#", "'#' (preprocessor)"), ("%:", "'%:' (preprocessor digraph)"), ("??", "'??' (trigraph)"),
+    for bad, thing in (("#", "'#' (preprocessor)"), ("%:", "'%:' (preprocessor digraph)"), ("??", "'??' (trigraph)"),
                       ("\\", "a backslash")):
         if bad in body:
-            raise ValueError(f"the body contains {what}: not allowed in a likelihood body")
+            raise ValueError(f"the body contains {thing}: not allowed in a {what} body")
     code = _strip_comments(body)
-    for bad, what in (('"', "a string literal"), ("'", "a character literal")):
+    for bad, thing in (('"', "a string literal"), ("'", "a character literal")):
         if bad in code:
-            raise ValueError(f"the body contains {what}: not allowed in a likelihood body")
+            raise ValueError(f"the body contains {thing}: not allowed in a {what} body")
     for m in _IDENT.finditer(code):
         tok = m.group(0)
         if tok in ("asm", "__asm__", "__asm") or tok.startswith("__asm"):
-            raise ValueError(f"inline assembly ({tok!r}) is not allowed in a likelihood body")
+            raise ValueError(f"inline assembly ({tok!r}) is not allowed in a {what} body")
         if tok.startswith("__builtin"):
-            raise ValueError(f"compiler builtins ({tok!r}) are not allowed in a likelihood body; the vocabulary: "
-                             + ", ".join(VOCABULARY))
+            raise ValueError(f"compiler builtins ({tok!r}) are not allowed in a {what} body; the vocabulary: "
+                             + ", ".join(vocabulary))
         if tok.startswith("__"):
             raise ValueError(f"identifiers starting with '__' ({tok!r}) are reserved")
         if tok.lower().startswith("pgb_"):
             raise ValueError(f"identifiers starting with 'pgb_' ({tok!r}) are reserved for the prelude")
         if tok in _REFUSED_KEYWORDS:
-            raise ValueError(f"{tok!r} is not allowed in a likelihood body (local double / int variables only)")
+            raise ValueError(f"{tok!r} is not allowed in a {what} body (local double / int variables only)")
+        if sampler and tok == "y":
+            lineno = code.count("\n", 0, m.start()) + 1
+            raise ValueError(f"line {lineno}: a sampler body has no y -- it returns one replicated observation from "
+                             f"mu, aux and the params:\n    {body.splitlines()[lineno - 1].strip()}")
     depth = 0
     for ch in code:  # the body stays inside its function
         depth += ch == "{"
@@ -166,11 +191,12 @@ def validate(body: str, param_names, n_outputs: int = 1) -> tuple[str, ...]:
         raise ValueError("unbalanced '{' in the body")
     for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_]*)\s*\(", code):
         fn = m.group(1)
-        if fn in VOCABULARY or fn in _CALLABLE_KEYWORDS:
+        if fn in vocabulary or fn in _CALLABLE_KEYWORDS:
             continue
         lineno = code.count("\n", 0, m.start()) + 1
-        raise CompileError(f"line {lineno}: {fn!r} is not in the likelihood vocabulary:\n    "
-                           f"{body.splitlines()[lineno - 1].strip()}\nthe vocabulary: {vocabulary_text()}")
+        raise CompileError(f"line {lineno}: {fn!r} is not in the {what} vocabulary"
+                           + (" (the random vocabulary belongs to sampler bodies)" if fn in RANDOM_VOCABULARY else "")
+                           + f":\n    {body.splitlines()[lineno - 1].strip()}\nthe vocabulary: {vocabulary_text(sampler)}")
     if K > 1:
         for m in re.finditer(r"\bmu\b(\s*\[\s*([0-9]+)\s*\])?", code):
             lineno = code.count("\n", 0, m.start()) + 1
@@ -196,7 +222,7 @@ def uses_tables(body: str) -> bool:
 def _header_files() -> list[str]:
     files = [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
     files += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
-    return files + [TU, TU_POINTWISE]
+    return files + [TU, TU_POINTWISE, TU_SAMPLER]
 
 
 def headers_hash() -> int:
@@ -230,11 +256,11 @@ def cache_dir() -> str:
 
 
 def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1, linear: bool = False,
-              pointwise: bool = False) -> str:
+              pointwise: bool = False, sampler: bool = False) -> str:
     h = hashlib.sha256()
     h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
                          "n_outputs": int(n_outputs), "linear": bool(linear),
-                         **({"pointwise": True} if pointwise else {}),
+                         **({"pointwise": True} if pointwise else {}), **({"sampler": True} if sampler else {}),
                          "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
                          "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
                         sort_keys=True).encode())
@@ -268,8 +294,8 @@ def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1, line
     ])
 
 
-def _body_text(body: str) -> str:
-    return '#line 1 "loglik body"\n' + body + "\n"
+def _body_text(body: str, sampler: bool = False) -> str:
+    return f'#line 1 "{"sampler" if sampler else "loglik"} body"\n' + body + "\n"
 
 
 def _host_source(body: str, names, n_outputs: int = 1) -> str:
@@ -342,18 +368,18 @@ int pgb_compiled_eval_rows(void* ctx, const double* y, const double* mu, int64_t
 """
 
 
-def _compile_error(stderr: str, body: str, side: str) -> CompileError:
+def _compile_error(stderr: str, body: str, side: str, sampler: bool = False) -> CompileError:
     lines = body.splitlines()
     msgs = []
-    for m in re.finditer(r"loglik body:(\d+):(?:\d+:)?\s*(?:fatal )?error:\s*(.*)", stderr):
+    for m in re.finditer(r"(?:loglik|sampler) body:(\d+):(?:\d+:)?\s*(?:fatal )?error:\s*(.*)", stderr):
         ln = int(m.group(1))
         src = lines[ln - 1].strip() if 1 <= ln <= len(lines) else ""
         msgs.append(f"line {ln}: {m.group(2).strip()}\n    {src}")
     if not msgs:
         tail = [ln for ln in stderr.splitlines() if "error" in ln][:5]
         msgs = tail or [stderr.strip()[-2000:]]
-    return CompileError(f"the likelihood body does not compile ({side}):\n" + "\n".join(msgs[:5])
-                        + f"\nthe vocabulary: {vocabulary_text()}")
+    return CompileError(f"the {'sampler' if sampler else 'likelihood'} body does not compile ({side}):\n"
+                        + "\n".join(msgs[:5]) + f"\nthe vocabulary: {vocabulary_text(sampler)}")
 
 
 def kernel_resources(code_object_path: str, kernel: str = "k_loglik_compiled") -> dict:
@@ -524,6 +550,161 @@ def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs
     return b
 
 
+def _sampler_host_source(body: str, names, n_outputs: int = 1) -> str:
+    """The host build of a SAMPLER body: ``pgb_compiled_draw`` evaluates it over a ``[D][K][n]`` array of predictors
+    the way ``k_ppc_compiled`` does on the device -- the reference of every device test."""
+    params = "".join(f", const double {nm}" for nm in names)
+    args = "".join(f", prm[{i}]" for i in range(len(names)))
+    K = int(n_outputs)
+    mu_decl = "double mu" if K == 1 else "const double* mu"
+    k_enum = "" if K == 1 else f"  enum {{ K = {K} }};\n"
+    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood's sampler body */
+#include <stdint.h>
+#include <stddef.h>
+#define PGB_COMPILED_NO_ENTRY_POINTS
+#include "pgbart_spec.h"
+#include "pgbart_compiled.h"
+#include "pgbart_ppc.h"
+#define PGB_CL_EXPT (pgb_cl_rng->tb->expt)
+#define PGB_CL_LOGT (pgb_cl_rng->tb->logt)
+#define PGB_CL_LPHI (pgb_cl_rng->tb->lphi)
+#define PGB_COMPILED_VOCABULARY
+#define PGB_COMPILED_SAMPLER_VOCABULARY
+#include "pgbart_compiled.h"
+static double pgb_compiled_sampler_user(pgb_ppc_ctx* pgb_cl_rng, {mu_decl}, double aux{params}) {{
+{k_enum}{_body_text(body, True)}}}
+#define PGB_COMPILED_VOCABULARY_END
+#include "pgbart_compiled.h"
+/* out[D][n] (or NULL) of mu[D][K][n] at global rows row0 .. row0 + n; params[D][n_params]; aux[n] or NULL (0.0); y[n]
+ * and pit[2][n] (added to) or NULL; flags[2] = (capped, exhausted) pairs */
+int pgb_compiled_draw(const double* mu, int D, int64_t n, uint64_t row0, const double* params, int n_params,
+                      const double* aux, uint64_t seed, double* out, const double* y, int32_t* pit, int64_t* flags) {{
+  const pgb_lltabs tb = pgb_lltabs_default();
+  flags[0] = flags[1] = 0;
+  for (int d = 0; d < D; ++d) {{
+    const double* prm = params + (size_t)d * (size_t)n_params;
+    for (int64_t i = 0; i < n; ++i) {{
+      double m[{K}];
+      for (int k = 0; k < {K}; ++k) m[k] = mu[((size_t)d * {K} + (size_t)k) * (size_t)n + (size_t)i];
+      pgb_ppc_ctx ctx;
+      uint32_t fl = 0;
+      pgb_ppc_ctx_begin(&ctx, seed, (uint32_t)d, row0 + (uint64_t)i, &tb);
+      const double v = pgb_ppc_ctx_end(&ctx, pgb_compiled_sampler_user(&ctx, {"m[0]" if K == 1 else "m"}, aux ? aux[i] : 0.0{args}), &fl);
+      if (fl & PGB_PPC_CAPPED) ++flags[0];
+      if (fl & PGB_PPC_EXHAUSTED) ++flags[1];
+      if (out) out[(size_t)d * (size_t)n + (size_t)i] = v;
+      if (y) {{
+        int below, equal;
+        pgb_ppc_compare(v, y[i], &below, &equal);
+        pit[i] += below;
+        pit[(size_t)n + (size_t)i] += equal;
+      }}
+    }}
+  }}
+  (void)n_params;
+  return 0;
+}}
+"""
+
+
+class CompiledSampler:
+    """One build of a SAMPLER body: the code object (``code``: ``k_ppc_compiled``, mark 2), the host library
+    (``host_lib``), the kernel's resource usage (``resources``), the cache ``key``."""
+
+    def __init__(self, key, body, param_names, code, host_lib, resources, compile_seconds, cached, n_outputs=1):
+        self.key, self.body, self.param_names = key, body, tuple(param_names)
+        self.n_outputs = int(n_outputs)
+        self.code, self.host_lib, self.resources = code, host_lib, resources
+        self.compile_seconds, self.cached = compile_seconds, cached
+        self._host = None
+
+    @property
+    def n_params(self) -> int:
+        return len(self.param_names)
+
+    def host_draw(self, mu, params=None, aux=None, seed=0, row0=0, y=None):
+        """The host build of the body over ``mu`` ``(D, K, n)`` (the offset already added), ``params``
+        ``(D, n_params)``, ``aux`` ``(n,)`` or ``None``, at global rows ``row0 ..`` -> (values ``(D, n)``, PIT counts
+        ``(2, n)`` int32 against ``y`` or ``None``, ``(n_capped, n_exhausted)``): what ``pgb_ppc_draw_compiled`` gives
+        for the same arguments, bit for bit."""
+        mu = np.ascontiguousarray(mu, np.float64)
+        if mu.ndim != 3 or mu.shape[1] != self.n_outputs:
+            raise ValueError(f"mu must be (D, K, n) with K = {self.n_outputs}, got {mu.shape}")
+        D, _, n = mu.shape
+        par = np.zeros((D, 0)) if params is None else np.ascontiguousarray(params, np.float64).reshape(D, -1)
+        if par.shape[1] != self.n_params:
+            raise ValueError(f"params must be (D, {self.n_params}), got {par.shape}")
+        ax = None if aux is None else np.ascontiguousarray(aux, np.float64).ravel()
+        if ax is not None and ax.size != n:
+            raise ValueError(f"aux must hold n = {n} values")
+        yy = None if y is None else np.ascontiguousarray(y, np.float64).ravel()
+        if yy is not None and yy.size != n:
+            raise ValueError(f"y must hold n = {n} values")
+        if self._host is None:
+            f = C.CDLL(self.host_lib).pgb_compiled_draw
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
+                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            self._host = f
+        out = np.empty((D, n))
+        pit = None if yy is None else np.zeros((2, n), np.int32)
+        flags = np.zeros(2, np.int64)
+        rc = self._host(mu.ctypes.data, D, n, int(row0), par.ctypes.data if par.size else None, self.n_params,
+                        None if ax is None else ax.ctypes.data, int(seed), out.ctypes.data,
+                        None if yy is None else yy.ctypes.data, None if pit is None else pit.ctypes.data, flags.ctypes.data)
+        if rc != 0:
+            raise CompileError(f"pgb_compiled_draw returned {rc}")
+        return out, pit, (int(flags[0]), int(flags[1]))
+
+
+def compile_sampler(body: str, param_names=(), n_outputs: int = 1) -> CompiledSampler:
+    """Compile the SAMPLER body ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) of ``n_outputs`` predictors
+    into ``k_ppc_compiled`` (``csrc/k_ppc_compiled.hip``) and its host evaluator -- or take them from the cache.  The
+    kernel reads no particle record: one object serves both particle builds."""
+    K = check_outputs(n_outputs)
+    names = validate(body, param_names, K, sampler=True)
+    key = cache_key(body, names, 64, K, sampler=True)
+    root = cache_dir()
+    os.makedirs(root, exist_ok=True)
+    co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
+    if os.path.exists(meta_path) and os.path.exists(co_path) and os.path.exists(so_path):
+        with open(meta_path) as fh:
+            meta = json.load(fh)
+        with open(co_path, "rb") as fh:
+            code = fh.read()
+        return CompiledSampler(key, body, names, code, so_path, meta["resources"], 0.0, True, K)
+    t0 = time.perf_counter()
+    with tempfile.TemporaryDirectory(prefix="pgb_jit_") as tmp:
+        src = os.path.join(tmp, "host.c")
+        with open(src, "w") as fh:
+            fh.write(_sampler_host_source(body, names, K))
+        so_tmp = os.path.join(tmp, "host.so")
+        r = subprocess.run(["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", src,
+                            "-o", so_tmp, "-lm"], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise _compile_error(r.stderr, body, "host", sampler=True)
+        with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
+            fh.write(_body_defs(names, 64, False, K))
+        with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
+            fh.write(_body_text(body, True))
+        co_tmp = os.path.join(tmp, "k.co")
+        cmd = [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, f"-I{CSRC}", f"-I{tmp}", "-w", TU_SAMPLER, "-o", co_tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise _compile_error(r.stderr, body, "device", sampler=True)
+        resources = kernel_resources(co_tmp, "k_ppc_compiled")
+        seconds = time.perf_counter() - t0
+        with open(co_tmp, "rb") as fh:
+            code = fh.read()
+        with open(so_tmp, "rb") as fh:
+            host = fh.read()
+    _write_atomic(co_path, code)
+    _write_atomic(so_path, host)
+    meta = {"sampler": body, "params": list(names), "n_outputs": K, "resources": resources, "compile_seconds": seconds}
+    _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
+    return CompiledSampler(key, body, names, code, so_path, resources, seconds, False, K)
+
+
 class CompiledLikelihood:
     """A per-row log-likelihood written as a C function body, compiled for the GPU at run time.
 
@@ -554,20 +735,43 @@ class CompiledLikelihood:
 
     >>> CompiledLikelihood("double u = (y - mu) / b;  return -(u * (u < 0.0 ? q - 1.0 : q));",
     ...                    params={"b": 0.25, "q": "q_var"})            # doctest: +SKIP
+
+    ``sampler`` (optional) says how to DRAW one observation: the inside of ``double r(double mu, double aux, const
+    double <param>...)`` -- the same ``mu`` (or ``mu[0] .. mu[K-1]``), ``aux`` and params, and no ``y`` (a sampler body
+    that names ``y`` is refused) -- which returns one replicated observation.  With it the posterior predictive calls
+    (``posterior_predictive``, ``predictive_summary``, ``predictive_pit``, ``loo_pit``, ``loo_predictive(kind="y")``)
+    take the likelihood; without it they refuse it, and nothing else changes.  A sampler body calls the vocabulary
+    above plus, in sampler bodies only, ``uniform()`` ([0, 1)), ``uniform_open()`` ((0, 1)), ``normal()``,
+    ``gamma(a)``, ``poisson(lam)`` and the helpers ``sqrt(x)``, ``floor(x)`` -- the exact samplers of the built-in
+    families (``include/pgbart_ppc.h``).  A value is a function of the seed, the position of the draw, the global row
+    and the inputs; a body may call a random function repeatedly (every call is a fresh, independent value; at most
+    1024 calls of one kind per evaluation; calls of one kind are numbered in execution order, so two of them in ONE
+    expression -- ``normal() - normal()`` -- may be numbered differently by the host and the device compiler: give
+    them statements of their own where the bits matter).  A non-finite result is capped and counted (``n_capped``).  The body owns
+    its domain: the params are only checked to be finite.  No param may carry a name of the random vocabulary when
+    there is a sampler body.
+
+    >>> CompiledLikelihood(zip_density, params={"pi": "pi"},
+    ...                    sampler="return uniform() < pi ? 0.0 : poisson(exp(mu));")   # doctest: +SKIP
     """
 
     family = "compiled"
 
-    def __init__(self, body: str, params=None, aux=None, n_outputs: int = 1):
+    def __init__(self, body: str, params=None, aux=None, n_outputs: int = 1, sampler=None):
         self.body = body
+        self.sampler = sampler
         self.n_outputs = check_outputs(n_outputs)
         self.param_spec = dict(params or {})
         self.param_names = validate(body, list(self.param_spec), self.n_outputs)
+        if sampler is not None:  # (before any compiler runs)
+            validate(sampler, self.param_names, self.n_outputs, sampler=True)
         self.aux = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).ravel()
         if self.aux is not None and not np.all(np.isfinite(self.aux)):
             raise ValueError("aux must be finite")
         self._builds = {}
         self.compiled(64)  # (errors surface here, not at the first step)
+        if sampler is not None:
+            self.compiled_sampler()
 
     def compiled(self, max_particles: int = 64, linear: bool = False, pointwise: bool = False) -> CompiledLoglik:
         mp = 128 if int(max_particles) > 64 and not pointwise else 64
@@ -577,13 +781,27 @@ class CompiledLikelihood:
                                              bool(pointwise))
         return self._builds[k]
 
+    @property
+    def has_sampler(self) -> bool:
+        return self.sampler is not None
+
+    def compiled_sampler(self) -> CompiledSampler:
+        """The build of the sampler body: the code object of ``k_ppc_compiled``, the host library (``host_draw``) and
+        the kernel's resources."""
+        if self.sampler is None:
+            raise CompileError("the likelihood has no sampler body (CompiledLikelihood(..., sampler=...))")
+        if "sampler" not in self._builds:
+            self._builds["sampler"] = compile_sampler(self.sampler, self.param_names, self.n_outputs)
+        return self._builds["sampler"]
+
     def params(self, point=None):
         from .pgbart import _from_point
 
         return [_from_point(v, point) for v in self.param_spec.values()]
 
     def __getstate__(self):
-        return {"body": self.body, "params": self.param_spec, "aux": self.aux, "n_outputs": self.n_outputs}
+        return {"body": self.body, "params": self.param_spec, "aux": self.aux, "n_outputs": self.n_outputs,
+                "sampler": self.sampler}
 
     def __setstate__(self, d):
-        self.__init__(d["body"], d["params"], d["aux"], d.get("n_outputs", 1))
+        self.__init__(d["body"], d["params"], d["aux"], d.get("n_outputs", 1), d.get("sampler"))

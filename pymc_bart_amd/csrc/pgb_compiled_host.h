@@ -43,6 +43,9 @@ extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64
     why = "the layout record could not be read";
   else if (rec.magic != PGB_COMPILED_MAGIC)
     why = "the layout record is not one of a compiled likelihood";
+  else if (rec.pointwise == PGB_COMPILED_MARK_SAMPLER)
+    why = "the code object is one built from a sampler body (" PGB_PPC_COMPILED_KERNEL ", mark 2): pgb_set_loglik_code "
+          "takes a sampler's pass kernel";
   else if (rec.max_particles != PGB_MAX_PARTICLES)
     why = PGB_MAX_PARTICLES == 64 ? "the code object was built for another particle build (this library takes 64)"
                                   : "the code object was built for another particle build (this library takes 128)";

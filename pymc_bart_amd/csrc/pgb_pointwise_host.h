@@ -16,17 +16,27 @@ struct PwScratch {
   }
 };
 
-// the code object of a compiled body for this call: loaded, its layout record held against the call's, never launched
-// when they differ (the message names both sides)
-static int pw_load_code(const pgb_pointwise_lik* lik, int K, PwScratch* sc, hipFunction_t* fn) {
-  if (!lik->code_object || lik->code_bytes < 64) return fail(PGB_E_INVALID, "the compiled family needs a code object");
-  const unsigned char* b = (const unsigned char*)lik->code_object;
+// what a layout record's mark says the code object is (the words follow "one")
+static const char* compiled_mark_name(int mark) {
+  return mark == PGB_COMPILED_MARK_PASS        ? "built without pointwise=True (a sampler's pass kernel, " PGB_COMPILED_KERNEL ")"
+         : mark == PGB_COMPILED_MARK_POINTWISE ? "built with pointwise=True (" PGB_POINTWISE_KERNEL ")"
+         : mark == PGB_COMPILED_MARK_SAMPLER   ? "built from a sampler body (" PGB_PPC_COMPILED_KERNEL ")"
+                                               : "of an unknown kind";
+}
+
+// the code object of a compiled body for one call of `entry` (pgb_pointwise_loglik: mark 1, pgb_ppc_draw_compiled:
+// mark 2): loaded into *mod (the caller unloads it), its layout record held against the call's, never launched when
+// they differ (the message names both sides).  k_side: how the call's K reads in a message.
+static int compiled_load_code(const void* code_object, int64_t code_bytes, int n_params, int K, const char* k_side,
+                              int want_mark, const char* entry, hipModule_t* mod, hipFunction_t* fn) {
+  if (!code_object || code_bytes < 64) return fail(PGB_E_INVALID, "the compiled family needs a code object");
+  const unsigned char* b = (const unsigned char*)code_object;
   if (!(b[0] == 0x7f && b[1] == 'E' && b[2] == 'L' && b[3] == 'F'))
     return fail(PGB_E_INVALID, "not a gfx950 code object (no ELF header): compile it with pymc_bart_amd.compiled");
-  hipError_t e = hipModuleLoadData(&sc->mod, lik->code_object);
+  hipError_t e = hipModuleLoadData(mod, code_object);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    sc->mod = nullptr;
+    *mod = nullptr;
     snprintf(g_err, sizeof g_err, "the code object does not load: %s", hipGetErrorString(e));
     return PGB_E_INVALID;
   }
@@ -34,15 +44,15 @@ static int pw_load_code(const pgb_pointwise_lik* lik, int K, PwScratch* sc, hipF
   memset(&rec, 0, sizeof rec);
   hipDeviceptr_t gp = nullptr;
   size_t gbytes = 0;
-  if (hipModuleGetGlobal(&gp, &gbytes, sc->mod, PGB_COMPILED_LAYOUT) != hipSuccess || gbytes != sizeof rec) {
+  if (hipModuleGetGlobal(&gp, &gbytes, *mod, PGB_COMPILED_LAYOUT) != hipSuccess || gbytes != sizeof rec) {
     (void)hipGetLastError();
     return fail(PGB_E_INVALID, "the code object has no layout record " PGB_COMPILED_LAYOUT);
   }
   HIPCHK(hipMemcpyDtoH(&rec, gp, sizeof rec));
   if (rec.magic != PGB_COMPILED_MAGIC) return fail(PGB_E_INVALID, "the layout record is not one of a compiled likelihood");
-  if (rec.pointwise != 1) {
-    snprintf(g_err, sizeof g_err, "the code object holds a sampler's pass kernel (built without pointwise=True, mark %d), "
-             "pgb_pointwise_loglik takes one built with pointwise=True (" PGB_POINTWISE_KERNEL ")", (int)rec.pointwise);
+  if (rec.pointwise != want_mark) {
+    snprintf(g_err, sizeof g_err, "the code object is one %s, mark %d: %s takes one %s", compiled_mark_name(rec.pointwise),
+             (int)rec.pointwise, entry, compiled_mark_name(want_mark));
     return PGB_E_INVALID;
   }
   if (PGB_HEADERS_HASH == 0ull || rec.headers_hash != (uint64_t)PGB_HEADERS_HASH) {
@@ -50,19 +60,20 @@ static int pw_load_code(const pgb_pointwise_lik* lik, int K, PwScratch* sc, hipF
              "(%016llx)", (unsigned long long)rec.headers_hash, (unsigned long long)PGB_HEADERS_HASH);
     return PGB_E_INVALID;
   }
-  if (rec.n_params != lik->n_params) {
+  if (rec.n_params != n_params) {
     snprintf(g_err, sizeof g_err, "the code object was compiled for %d params, the call gives n_params = %d",
-             (int)rec.n_params, (int)lik->n_params);
+             (int)rec.n_params, n_params);
     return PGB_E_INVALID;
   }
   if (rec.n_outputs != K) {
-    snprintf(g_err, sizeof g_err, "the code object was compiled for %d outputs, the trees have n_outputs = %d",
-             (int)rec.n_outputs, K);
+    snprintf(g_err, sizeof g_err, "the code object was compiled for %d outputs, %s = %d", (int)rec.n_outputs, k_side, K);
     return PGB_E_INVALID;
   }
-  if (hipModuleGetFunction(fn, sc->mod, PGB_POINTWISE_KERNEL) != hipSuccess) {
+  const char* kernel = want_mark == PGB_COMPILED_MARK_SAMPLER ? PGB_PPC_COMPILED_KERNEL : PGB_POINTWISE_KERNEL;
+  if (hipModuleGetFunction(fn, *mod, kernel) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(PGB_E_INVALID, "the code object has no kernel " PGB_POINTWISE_KERNEL);
+    snprintf(g_err, sizeof g_err, "the code object has no kernel %s", kernel);
+    return PGB_E_INVALID;
   }
   return PGB_OK;
 }
@@ -120,7 +131,8 @@ extern "C" int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t*
   PwScratch sc;
   hipFunction_t fn = nullptr;
   if (compiled) {
-    rc = pw_load_code(lik, K, &sc, &fn);
+    rc = compiled_load_code(lik->code_object, lik->code_bytes, lik->n_params, K, "the trees have n_outputs",
+                            PGB_COMPILED_MARK_POINTWISE, "pgb_pointwise_loglik", &sc.mod, &fn);
     if (rc != PGB_OK) return rc;
   }
   // ---- the rows' columns: finite y / aux, a bounded offset (the tables are addressed by the predictor's bits)

@@ -80,6 +80,7 @@
 #include "k_rowsummary.h"
 #include "k_diag.h"
 #include "k_ppc.h"
+#include "pgb_ppc_compiled_host.h"
 #include "k_pdp.h"
 #include "k_shap.h"
 #include "k_shap_interaction.h"

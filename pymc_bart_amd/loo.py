@@ -20,14 +20,12 @@ HIP backend only.  At most :data:`MAX_DRAWS` draws, and a tail of at most :data:
 
 from __future__ import annotations
 
-import ctypes as C
 import math
 import warnings
 
 import numpy as np
 
-from . import _abi
-from ._stored import check_seed, fill_lik, hip_only, matrix_blocks
+from ._stored import check_seed, hip_only, matrix_blocks
 from .pointwise import ScoringJob
 
 MAX_DRAWS = 16384  # PGB_PSIS_MAX_DRAWS (include/pgbart_psis.h)
@@ -195,7 +193,7 @@ def _expect_job(sampler, X, y, likelihood, points, offset, draws, reff, random_s
     job = ScoringJob(sampler, X, y, likelihood, points, offset, draws)
     M = tail_length(job.D, reff)
     seed = check_seed(random_seed)
-    if family is not None:
+    if family is not None and family != "compiled":  # (a sampler body owns its domain)
         check_domain(family, job.params)
     return job, M, seed
 
@@ -210,8 +208,9 @@ def _run_expect(job, M: int, seed: int, mode: str):
     psis = np.empty((2, n))
     E = np.empty((K if mode == "mu" else 1, n_e, n))
     info = {"n_capped": 0, "n_exhausted": 0}
-    flags = (C.c_int64 * 2)()
-    lik = fill_lik(_abi.PpcLik(), job) if mode != "mu" else None
+    from .predictive import Replicator
+
+    replicate = []  # (made with the first block: it needs the backend's library)
 
     def expect(be, blk):
         lib, mem, md, od, nb, r0, r1 = be.lib, be.mem, blk.md, blk.od, blk.nb, blk.r0, blk.r1
@@ -223,18 +222,16 @@ def _run_expect(job, M: int, seed: int, mode: str):
                 o = _expect_block(lib, mem, md, D, nb, nb, M, mem.ptr(gd) + 8 * k * nb, K * nb, None, kind)
                 E[k, :, r0:r1] = o[2:]
         else:
-            lik.offset_dev = None if od is None else mem.ptr(od)
+            if not replicate:
+                replicate.append(Replicator(lib, job, seed))
             rd = gd if K == 1 else mem.empty((D * nb,), np.float64)  # (K = 1: in place)
-            rc = lib.ppc_entry_point()(mem.ptr(gd), D, K, nb, nb, r0, C.byref(lik), seed, mem.ptr(rd), nb, None, None, flags,
-                                       mem.stream_ptr)
-            lib.check(rc, "pgb_ppc_draw")
-            info["n_capped"] += int(flags[0])
-            info["n_exhausted"] += int(flags[1])
+            replicate[0](be, gd, nb, r0, od, rd)
+            info.update(replicate[0].info)
             o = _expect_block(lib, mem, md, D, nb, nb, M, mem.ptr(rd), nb, blk.yd if mode == "pit" else None, kind)
             E[0, :, r0:r1] = o[2:]
         psis[:, r0:r1] = o[:2]
 
-    scratch = 2 + n_e + K * D + (D if K > 1 and mode != "mu" else 0)
+    scratch = 2 + n_e + K * D + (D if K > 1 and mode != "mu" else 0) + (1 if mode != "mu" and job.aux is not None else 0)
     _, stats, clamped = job.run(matrix=True, summary=True, on_block=expect, scratch=scratch)
     return psis, E, stats, clamped, info
 
@@ -247,7 +244,8 @@ def loo_pit(sampler, X, y, likelihood, points=None, offset=None, draws=None, ref
     position of the draw and global row: the result does not depend on ``PGB_PW_BLOCK_BYTES``).  Uniform for a
     calibrated model; the mid-p form keeps that for the discrete families.
 
-    The arguments are :func:`loo`'s; the compiled and callback families have no sampler and are refused.  Returns
+    The arguments are :func:`loo`'s; a compiled likelihood without a sampler body, and the callback family, have no
+    sampler and are refused.  Returns
     :func:`loo`'s dict plus ``loo_pit``, ``n_capped`` and ``n_exhausted`` (``include/pgbart_ppc.h``).  Nothing of size
     ``draws x rows`` reaches the host."""
     job, M, seed = _expect_job(sampler, X, y, likelihood, points, offset, draws, reff, random_seed, "pit")

@@ -12,7 +12,9 @@ the launch geometry.
 * :func:`predictive_pit` returns the PIT values of observed ``y`` (mid-p: ``(below + equal / 2) / D``); no matrix is
   written at all.
 
-The ten built-in families have a sampler; the compiled and callback families have a log density only and are refused.
+The ten built-in families have a sampler, and so has a :class:`~pymc_bart_amd.CompiledLikelihood` with a sampler body
+(``sampler=``: ``pgb_ppc_draw_compiled`` runs it, ``k_ppc_compiled``); a compiled likelihood without a sampler body, and
+the callback family, have a log density only and are refused.
 Rejection samplers are bounded: pairs that exhausted their attempts (``n_exhausted``) or met a cap (``n_capped``: a
 Poisson rate above 2^30, a non-finite value) are counted, never silent.  HIP backend only.
 """
@@ -31,6 +33,8 @@ from .summary import DEFAULT_HDI_PROB, DEFAULT_QUANTILES, result, spec, summary_
 
 def check_family(likelihood) -> str:
     family = getattr(likelihood, "family", None)
+    if family == "compiled" and getattr(likelihood, "sampler", None) is not None:
+        return family
     if family in ("callback", "compiled"):
         raise ValueError(f"the {family} family has a log density only, no sampler: posterior predictive draws take the "
                          f"built-in families ({', '.join(FAMILY_PARAMS)})")
@@ -50,21 +54,80 @@ def check_domain(family: str, params: np.ndarray) -> None:
                          f"0 < q < 1): {params[d].tolist()}")
 
 
+def check_aux(likelihood, n: int):
+    """The aux column of a compiled likelihood against the ``n`` rows of ``X`` (``None`` without one)."""
+    aux = getattr(likelihood, "aux", None)
+    if aux is None:
+        return None
+    if aux.size != n:
+        raise ValueError(f"the compiled likelihood's aux must hold one value per row ({n}), got {aux.size}")
+    return np.ascontiguousarray(aux, np.float64)
+
+
+class Replicator:
+    """The replicating call of one job -- ``pgb_ppc_draw`` of a built-in family or ``pgb_ppc_draw_compiled`` of a
+    compiled likelihood's sampler body -- for a block of rows, and the flag counts summed over the blocks.  ``job``
+    gives ``family``, ``n_par``, ``params``, ``D``, ``K`` and, for the compiled family, ``likelihood`` and ``aux``."""
+
+    def __init__(self, lib, job, seed: int):
+        self.job, self.seed = job, seed
+        self.compiled = job.family == "compiled"
+        if self.compiled:
+            build = job.likelihood.compiled_sampler()
+            self._code = C.create_string_buffer(build.code, len(build.code))
+            self.lik = lik = _abi.PpcCode()
+            lik.code_object, lik.code_bytes = C.cast(self._code, C.c_void_p), len(build.code)
+            lik.n_params = job.n_par
+            lik.params_host = job.params.ctypes.data if job.n_par else None
+            self.call, self.name = lib.ppc_compiled_entry_point(), "pgb_ppc_draw_compiled"
+        else:
+            self.lik = fill_lik(_abi.PpcLik(), job)
+            self.call, self.name = lib.ppc_entry_point(), "pgb_ppc_draw"
+        self.flags = (C.c_int64 * 2)()
+        self.capped = self.exhausted = 0
+
+    def __call__(self, be, gd, nb: int, r0: int, od=None, rd=None, yd=None, pd=None):
+        """``gd`` ``[D][K][nb]`` (the predictors of rows ``r0 ..``) -> ``rd`` ``[D][nb]`` (or ``None``) and the PIT
+        counts ``pd`` against ``yd`` (or ``None``)."""
+        lib, mem, job = be.lib, be.mem, self.job
+        self.lik.offset_dev = None if od is None else mem.ptr(od)
+        ad = None
+        if self.compiled:
+            ad = None if job.aux is None else mem.from_host(job.aux[r0:r0 + nb])
+            self.lik.aux_dev = None if ad is None else mem.ptr(ad)
+        rc = self.call(mem.ptr(gd), job.D, job.K, nb, nb, r0, C.byref(self.lik), self.seed,
+                       None if rd is None else mem.ptr(rd), nb, None if yd is None else mem.ptr(yd),
+                       None if pd is None else mem.ptr(pd), self.flags, mem.stream_ptr)
+        lib.check(rc, self.name)
+        del ad
+        self.capped += int(self.flags[0])
+        self.exhausted += int(self.flags[1])
+
+    @property
+    def info(self) -> dict:
+        return {"n_capped": self.capped, "n_exhausted": self.exhausted}
+
+
 class _Job(Job):
-    """One replicating call: the job base plus the family, its params in their domain, the seed and ``y`` for the PIT."""
+    """One replicating call: the job base plus the family, its params in their domain (a sampler body's: finite), the
+    body's ``aux``, the seed and ``y`` for the PIT."""
 
     def __init__(self, sampler, X, likelihood, points, offset, draws, excluded, random_seed, y=None, pit=False):
         super().__init__(sampler)
         self.family = check_family(likelihood)
-        self.n_par = FAMILY_PARAMS[self.family]
-        check_outputs(likelihood, self.family, self.K, FAMILY_OUTPUTS.get(self.family, 1))
+        self.likelihood = likelihood
+        compiled = self.family == "compiled"
+        self.n_par = len(likelihood.param_names) if compiled else FAMILY_PARAMS[self.family]
+        check_outputs(likelihood, self.family, self.K, self.K if compiled else FAMILY_OUTPUTS.get(self.family, 1))
         self.take_X(X)
         self.y = check_y(y, self.n) if pit else None
         self.take_offset(offset)
+        self.aux = check_aux(likelihood, self.n) if compiled else None
         self.take_excluded(excluded)
         self.take_draws(draws, "no draws to replicate")
         self.params = param_matrix(likelihood, points, self.D)
-        check_domain(self.family, self.params)
+        if not compiled:  # (a sampler body owns its domain)
+            check_domain(self.family, self.params)
         self.seed = check_seed(random_seed)
         self.take_history()
 
@@ -73,35 +136,28 @@ class _Job(Job):
         (2, n).  Each with (n_capped, n_exhausted)."""
         be = self.hip_backend("posterior predictive draws run")
         lib, mem = be.lib, be.mem
-        call = lib.ppc_entry_point()
+        replicate = Replicator(lib, self, self.seed)
         n, D, K, p = self.n, self.D, self.K, self.p
         Q = 0 if q is None else q.size
-        per_row = 8 * (p + K * (D + 1) + (D if K > 1 and mode != "pit" else 0) + (2 + Q + 2 if mode == "summary" else 0) + 2)
+        per_row = 8 * (p + K * (D + 1) + (D if K > 1 and mode != "pit" else 0) + (2 + Q + 2 if mode == "summary" else 0) + 2
+                       + (1 if self.aux is not None else 0))
         out = {"matrix": np.empty((D, n)), "summary": np.empty((2 + Q + 2, n)), "pit": np.empty((2, n), np.int64)}[mode]
-        lik = fill_lik(_abi.PpcLik(), self)
-        flags = (C.c_int64 * 2)()
-        capped = exhausted = 0
         for blk in self.blocks(be, per_row, predict=True):
             r0, r1, nb, md = blk.r0, blk.r1, blk.nb, blk.md
-            lik.offset_dev = None if blk.od is None else mem.ptr(blk.od)
             yd = pd = rd = None
             if mode == "pit":
                 yd = mem.from_host(self.y[r0:r1])
                 pd = mem.from_host(np.zeros(2 * nb, np.int32))
             else:
                 rd = md if K == 1 else mem.empty((D * nb,), np.float64)  # (K = 1: in place)
-            rc = call(mem.ptr(md), D, K, nb, nb, r0, C.byref(lik), self.seed, None if rd is None else mem.ptr(rd), nb,
-                      None if yd is None else mem.ptr(yd), None if pd is None else mem.ptr(pd), flags, mem.stream_ptr)
-            lib.check(rc, "pgb_ppc_draw")
-            capped += int(flags[0])
-            exhausted += int(flags[1])
+            replicate(be, md, nb, r0, blk.od, rd, yd, pd)
             if mode == "matrix":
                 out[:, r0:r1] = mem.to_host(rd).reshape(D, nb)
             elif mode == "summary":
                 out[:, r0:r1] = summary_block(lib, mem, rd, D, nb, nb, None, 0, q, hdi_k)
             else:
                 out[:, r0:r1] = mem.to_host(pd).reshape(2, nb)
-        return out, {"n_capped": capped, "n_exhausted": exhausted}
+        return out, replicate.info
 
 
 def posterior_predictive(sampler, X, likelihood, points=None, offset=None, draws=None, excluded=None, random_seed=0,
@@ -111,7 +167,8 @@ def posterior_predictive(sampler, X, likelihood, points=None, offset=None, draws
     family, 0 / 1 for the Bernoulli families).
 
     ``sampler``, ``likelihood``, ``points``, ``offset``: as :func:`~pymc_bart_amd.pointwise_log_likelihood` takes them
-    (the compiled and callback families have no sampler and are refused).  ``excluded``: covariates marginalised out
+    (a compiled likelihood without a sampler body, and the callback family, have no sampler and are refused; a
+    compiled likelihood's ``aux`` column belongs to the rows of ``X``).  ``excluded``: covariates marginalised out
     by the trees' own counts, as in ``sample_posterior``.  ``random_seed``: a value is a function of the seed, the
     POSITION of the draw in ``draws`` and the row index alone -- the same call gives the same array, whatever
     ``PGB_PW_BLOCK_BYTES`` says.  ``return_info``: also return ``{"n_capped", "n_exhausted"}``, the (draw, row) pairs

@@ -91,32 +91,7 @@ int pgb_compiled_probe(pgb_handle* h, const double* y, const double* mu, const d
 #endif
 #endif
 
-#endif /* PGBART_COMPILED_H */
-
-/* ------------------------------------------------------------------ vocabulary
- * (outside the include guard: a unit that compiles a body includes this header again around it)
- * The unit defines, right in front of the body:
- *   PGB_COMPILED_VOCABULARY                    then includes this header: the vocabulary is on
- *   PGB_CL_EXPT / PGB_CL_LOGT / PGB_CL_LPHI   the tables (host: pgb_tab_*(); device: the kernel's copies)
- * and behind it PGB_COMPILED_VOCABULARY_END (and includes this header again): the names are released.
- * The functions are macros so that the same text serves C (host) and HIP (device):
- *   exp, log         pgb_exp_t, pgb_log_t             (pgbart_spec.h: table-driven, the same bits on both sides)
- *   log_ndtr         pgb_lphi_t                       (log Phi, the probit family's function)
- *   softplus         pgb_softplus_t                   (log(1 + e^x))
- *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour)
- *   lgamma           pgb_cl_lgamma                    (log Gamma(x), x > 0: + - * / and pgb_log_t only)
- * A unit that compiles a SAMPLER BODY also defines PGB_COMPILED_SAMPLER_VOCABULARY, after it has included
- * pgbart_ppc.h, and has a `pgb_ppc_ctx* pgb_cl_rng` in scope around the body: the random vocabulary is on as well --
- *   uniform()        pgb_ppc_ctx_uniform       [0, 1)     uniform_open()   pgb_ppc_ctx_uniform_open   (0, 1)
- *   normal()         pgb_ppc_ctx_normal                   gamma(a)         pgb_ppc_ctx_gamma
- *   poisson(lam)     pgb_ppc_ctx_poisson
- *   sqrt(x)          pgb_psis_sqrt                        floor(x)         pgb_ppc_floor
- * -- with the addressing of repeated calls, the call cap and the flags as include/pgbart_ppc.h states them.  A
- * density body never sees these names: a param of a density-only likelihood may be called gamma. */
-#if defined(PGB_COMPILED_VOCABULARY) && !defined(PGB_COMPILED_VOCABULARY_ON)
-#define PGB_COMPILED_VOCABULARY_ON
-#ifndef PGB_COMPILED_VOCABULARY_FNS
-#define PGB_COMPILED_VOCABULARY_FNS
+/* ---- the functions behind the vocabulary (section "vocabulary" below); pgbart_logpdf.h uses pgb_cl_lgamma too */
 #include "pgbart_spec.h"
 /* fabs(-0.0) = +0.0, a NaN stays a NaN; fmin / fmax return the SECOND argument when the comparison fails (a NaN
  * in either) */
@@ -151,7 +126,31 @@ PGB_HD double pgb_cl_lgamma(double x, const double* logt) {
   if (p != 1.0) v = v - pgb_log_t(p, logt);
   return v;
 }
-#endif
+
+#endif /* PGBART_COMPILED_H */
+
+/* ------------------------------------------------------------------ vocabulary
+ * (outside the include guard: a unit that compiles a body includes this header again around it)
+ * The prelude of every such unit, pgbart_compiled_body.h, defines right in front of the body:
+ *   PGB_COMPILED_VOCABULARY                    then includes this header: the vocabulary is on
+ *   PGB_CL_EXPT / PGB_CL_LOGT / PGB_CL_LPHI   the tables (those of the function's first argument)
+ * and behind it PGB_COMPILED_VOCABULARY_END (and includes this header again): the names are released.
+ * The functions are macros so that the same text serves C (host) and HIP (device):
+ *   exp, log         pgb_exp_t, pgb_log_t             (pgbart_spec.h: table-driven, the same bits on both sides)
+ *   log_ndtr         pgb_lphi_t                       (log Phi, the probit family's function)
+ *   softplus         pgb_softplus_t                   (log(1 + e^x))
+ *   fabs, fmin, fmax explicit comparisons             (no builtin: the same NaN / signed-zero behaviour)
+ *   lgamma           pgb_cl_lgamma                    (log Gamma(x), x > 0: + - * / and pgb_log_t only)
+ * A unit that compiles a SAMPLER BODY also defines PGB_COMPILED_SAMPLER_VOCABULARY, after it has included
+ * pgbart_ppc.h, and has a `pgb_ppc_ctx* pgb_cl_rng` in scope around the body: the random vocabulary is on as well --
+ *   uniform()        pgb_ppc_ctx_uniform       [0, 1)     uniform_open()   pgb_ppc_ctx_uniform_open   (0, 1)
+ *   normal()         pgb_ppc_ctx_normal                   gamma(a)         pgb_ppc_ctx_gamma
+ *   poisson(lam)     pgb_ppc_ctx_poisson
+ *   sqrt(x)          pgb_psis_sqrt                        floor(x)         pgb_ppc_floor
+ * -- with the addressing of repeated calls, the call cap and the flags as include/pgbart_ppc.h states them.  A
+ * density body never sees these names: a param of a density-only likelihood may be called gamma. */
+#if defined(PGB_COMPILED_VOCABULARY) && !defined(PGB_COMPILED_VOCABULARY_ON)
+#define PGB_COMPILED_VOCABULARY_ON
 #define exp(x) pgb_exp_t((double)(x), PGB_CL_EXPT)
 #define log(x) pgb_log_t((double)(x), PGB_CL_LOGT)
 #define log_ndtr(x) pgb_lphi_t((double)(x), PGB_CL_LPHI)

@@ -32,13 +32,7 @@
 #define PGBART_LOGPDF_H
 
 #include "pgbart_spec.h"
-/* pgb_cl_lgamma: the vocabulary's log Gamma (pgbart_compiled.h), without leaving the vocabulary's macros on */
-#ifndef PGB_COMPILED_VOCABULARY_FNS
-#define PGB_COMPILED_VOCABULARY
-#include "pgbart_compiled.h"
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-#endif
+#include "pgbart_compiled.h" /* pgb_cl_lgamma: the vocabulary's log Gamma */
 
 #define PGB_PW_CHUNK 32 /* draws per chunk of the reduction over draws: part of the result's definition */
 #define PGB_PW_NPAR 4   /* prepared values per draw of a built-in family */

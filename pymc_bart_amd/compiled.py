@@ -1,26 +1,27 @@
 """Custom per-row likelihoods compiled at run time: family ``"compiled"`` (``include/pgbart_compiled.h``).
 
-The user writes the log-density of ONE observation as a short C function body; :func:`compile_loglik` turns it
-into
+The user writes the log-density of ONE observation as a short C function body -- and, optionally, a SAMPLER body: how
+to draw one observation.  One build path (:func:`_build`) turns a body into a gfx950 code object and a host library,
+both from committed units that read the same two generated files; how a body becomes a function is stated once, in
+``include/pgbart_compiled_body.h``.  The kinds of build (``_KINDS``):
 
-* a gfx950 code object: ``csrc/k_loglik_compiled.hip`` -- the library's one-output log-likelihood pass with the body
-  at every evaluation site -- compiled with the library's device flags plus ``--genco``.  The HIP library loads it
+* ``pass`` (:func:`compile_loglik`): ``csrc/k_loglik_compiled.hip`` -- the library's log-likelihood pass with the body
+  at every evaluation site, for one particle build, ``n_outputs = K`` predictors (``mu[0] .. mu[K-1]``) and constant
+  or, with ``linear=True``, linear leaves (``response="linear"`` / ``"mix"``).  The HIP library loads it
   (``pgb_set_loglik_code``) and the chain stays device-resident: no host round trip per SMC round;
-* a host function with the ``pgb_loglik_fn`` signature (gcc, the oracle's flags), which any CPU backend runs as
-  family ``"callback"`` -- natively, no Python in the per-row loop.
+* ``pointwise`` (``compile_loglik(..., pointwise=True)``): ``csrc/k_pointwise_compiled.hip`` -- the body inside the
+  posterior tree walk, for scoring a fit (:mod:`pymc_bart_amd.pointwise`);
+* ``sampler`` (:func:`compile_sampler`): ``csrc/k_ppc_compiled.hip`` -- the sampler body inside the replicating kernel
+  (:mod:`pymc_bart_amd.predictive`).
 
-Both sides evaluate the body with the same vocabulary (table-driven ``exp`` / ``log`` / ``log_ndtr`` /
-``softplus`` / ``lgamma`` on the tables of ``include/pgbart_spec.h``, explicit comparisons), so that a CPU backend
-checks the GPU chain bit for bit.  A body of ``n_outputs = K >= 2`` reads ``mu[0] .. mu[K-1]``: its code object is the
-library's K-vector pass; no CPU backend runs it (the callback family has one output), and its host build is an
-evaluator of rows (``pgb_compiled_eval_rows``) that the device's probe kernel is held to.  With ``linear=True`` the
-code object holds the library's linear-leaf pass instead (``response="linear"`` / ``"mix"``, one output or K): one pass
-kernel per code object, and HIP only -- the CPU backends' callback family has constant leaves.  With ``pointwise=True``
-the code object holds no pass kernel but ``k_pointwise_compiled`` (``csrc/k_pointwise_compiled.hip``): the body inside
-the posterior tree walk, for scoring a fit (:mod:`pymc_bart_amd.pointwise`).  A likelihood may also carry a SAMPLER body -- how to draw one observation --
-which :func:`compile_sampler` turns into a third kind of code object, ``k_ppc_compiled`` (``csrc/k_ppc_compiled.hip``),
-and a host evaluator (:mod:`pymc_bart_amd.predictive`).  Builds are cached on disk (``$PGB_JIT_CACHE``, default ``~/.cache/pymc_bart_amd/jit``) under a key over
-everything that goes into them.
+The host build (gcc, the oracle's flags) of a density is ``csrc/h_loglik_compiled.c``: for one output a function with
+the ``pgb_loglik_fn`` signature, which any CPU backend runs as family ``"callback"`` -- natively, no Python in the
+per-row loop; for K outputs (no CPU backend runs those: the callback family has one output and constant leaves) an
+evaluator of rows that the device's probe kernel is held to.  That of a sampler body is ``csrc/h_ppc_compiled.c``, the
+reference of the device's draws.  Both sides evaluate a body with the same vocabulary (table-driven ``exp`` / ``log`` /
+``log_ndtr`` / ``softplus`` / ``lgamma`` on the tables of ``include/pgbart_spec.h``, explicit comparisons), so that the
+CPU checks the GPU bit for bit.  Builds are cached on disk (``$PGB_JIT_CACHE``, default
+``~/.cache/pymc_bart_amd/jit``) under a key over everything that goes into them.
 """
 
 from __future__ import annotations
@@ -41,11 +42,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
-TU = os.path.join(CSRC, "k_loglik_compiled.hip")
-#: the unit of a POINTWISE code object (``compile_loglik(..., pointwise=True)``; include/pgbart_pointwise.h)
-TU_POINTWISE = os.path.join(CSRC, "k_pointwise_compiled.hip")
-#: the unit of a SAMPLER code object (``compile_sampler``; include/pgbart_ppc.h)
-TU_SAMPLER = os.path.join(CSRC, "k_ppc_compiled.hip")
+#: the kinds of build (the layout record's marks 0, 1, 2): the device unit, the host unit, the kernel whose resources
+#: are reported, the device build's extra defines.  The kind is part of the cache key (``cache_key``) and decides the
+#: meta record (``_build``); only a pass object depends on the particle build and on the kind of leaves
+_PARTICLES = "-DPGB_MAX_PARTICLES={mp}"
+_KINDS = {
+    "pass": ("k_loglik_compiled.hip", "h_loglik_compiled.c", "k_loglik_compiled", [_PARTICLES]),
+    "pointwise": ("k_pointwise_compiled.hip", "h_loglik_compiled.c", "k_pointwise_compiled", [_PARTICLES]),
+    "sampler": ("k_ppc_compiled.hip", "h_ppc_compiled.c", "k_ppc_compiled", []),
+}
 LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 #: the library's device flags (``__graft_entry__.HIPCC_FLAGS`` without ``-fPIC`` / ``-shared``; a test holds them equal)
@@ -220,14 +225,17 @@ def uses_tables(body: str) -> bool:
 
 # ---------------------------------------------------------------------------------------------------- keys, cache
 def _header_files() -> list[str]:
+    """What ``PGB_HEADERS_HASH`` covers, by rule: the headers of ``include/`` and ``csrc/`` and the units compiled at
+    run time, ``csrc/*_compiled.hip`` (device) and ``csrc/*_compiled.c`` (host).  ``__graft_entry__.build`` rebuilds
+    the library when one of them is newer."""
     files = [os.path.join(INCLUDE, f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
-    files += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
-    return files + [TU, TU_POINTWISE, TU_SAMPLER]
+    return files + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))
+                    if f.endswith((".h", "_compiled.hip", "_compiled.c"))]
 
 
 def headers_hash() -> int:
-    """64-bit hash of every header the code object and the library are built from (and of the unit itself): the
-    library is compiled with it (``-DPGB_HEADERS_HASH``) and refuses a code object that carries another."""
+    """64-bit hash of every file a code object, a host build and the library are built from (:func:`_header_files`):
+    the library is compiled with it (``-DPGB_HEADERS_HASH``) and refuses a code object that carries another."""
     h = hashlib.sha256()
     for f in _header_files():
         h.update(os.path.basename(f).encode() + b"\0")
@@ -257,10 +265,10 @@ def cache_dir() -> str:
 
 def cache_key(body: str, param_names, max_particles: int = 64, n_outputs: int = 1, linear: bool = False,
               pointwise: bool = False, sampler: bool = False) -> str:
+    kind = "sampler" if sampler else "pointwise" if pointwise else "pass"
     h = hashlib.sha256()
-    h.update(json.dumps({"body": body, "params": list(param_names), "max_particles": int(max_particles),
+    h.update(json.dumps({"kind": kind, "body": body, "params": list(param_names), "max_particles": int(max_particles),
                          "n_outputs": int(n_outputs), "linear": bool(linear),
-                         **({"pointwise": True} if pointwise else {}), **({"sampler": True} if sampler else {}),
                          "device_flags": DEVICE_FLAGS + GENCO_FLAGS, "host_flags": HOST_FLAGS,
                          "headers_hash": headers_hash(), "hipcc": _hipcc_version(hipcc_path())},
                         sort_keys=True).encode())
@@ -281,7 +289,8 @@ def _write_atomic(path: str, data: bytes) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------- the builds
-def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1, linear: bool = False) -> str:
+def _body_defs(names, explog: bool, n_outputs: int = 1, linear: bool = False) -> str:
+    """``pgb_compiled_body.inc``: what both compilers know about a body besides its text."""
     return "\n".join([
         f"#define PGB_COMPILED_NPARAMS {len(names)}",
         f"#define PGB_COMPILED_NOUT {int(n_outputs)}",
@@ -289,83 +298,15 @@ def _body_defs(names, max_particles: int, explog: bool, n_outputs: int = 1, line
         f"#define PGB_COMPILED_EXPLOG {1 if explog else 0}",
         f"#define PGB_HEADERS_HASH {headers_hash()}ull",
         "#define PGB_COMPILED_PARAMS " + "".join(f", const double {nm}" for nm in names),
-        "#define PGB_COMPILED_ARGS(P) " + "".join(f", (P).v[{i}]" for i in range(len(names))),
+        "#define PGB_COMPILED_ARGV(V) " + "".join(f", (V)[{i}]" for i in range(len(names))),
+        "#define PGB_COMPILED_ARGS(P) PGB_COMPILED_ARGV((P).v)",
         "",
     ])
 
 
 def _body_text(body: str, sampler: bool = False) -> str:
+    """``pgb_compiled_body_text.inc``: compiler messages count the user's lines."""
     return f'#line 1 "{"sampler" if sampler else "loglik"} body"\n' + body + "\n"
-
-
-def _host_source(body: str, names, n_outputs: int = 1) -> str:
-    params = "".join(f", const double {nm}" for nm in names)
-    args = "".join(f", c->params[{i}]" for i in range(len(names)))
-    K = int(n_outputs)
-    if K > 1:
-        return _host_source_k(body, params, args, K)
-    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood body */
-#include <stdint.h>
-#include <stddef.h>
-#define PGB_COMPILED_NO_ENTRY_POINTS
-#include "pgbart_spec.h"
-#include "pgbart_compiled.h"
-#define PGB_CL_EXPT pgb_tab_exp()
-#define PGB_CL_LOGT pgb_tab_log()
-#define PGB_CL_LPHI pgb_tab_lphi()
-#define PGB_COMPILED_VOCABULARY
-#include "pgbart_compiled.h"
-static double pgb_compiled_user(double y, double mu, double aux{params}) {{
-{_body_text(body)}}}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-typedef struct {{
-  const double* aux;
-  double params[PGB_COMPILED_MAX_PARAMS];
-}} pgb_compiled_ctx;
-/* pgb_loglik_fn: the row index selects aux; the library clamps and quantises the values */
-int pgb_compiled_loglik(void* ctx, const int64_t* row, const double* y, const double* mu, int64_t n, double* out) {{
-  const pgb_compiled_ctx* c = (const pgb_compiled_ctx*)ctx;
-  for (int64_t i = 0; i < n; ++i) out[i] = pgb_compiled_user(y[i], mu[i], c->aux ? c->aux[row[i]] : 0.0{args});
-  return 0;
-}}
-"""
-
-
-def _host_source_k(body: str, params: str, args: str, K: int) -> str:
-    """The host build of a K-vector body: no sampler runs it (no CPU backend has a K-vector callback family), it
-    evaluates given rows -- the reference the device's probe kernel is held to."""
-    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood body of {K} outputs */
-#include <stdint.h>
-#include <stddef.h>
-#define PGB_COMPILED_NO_ENTRY_POINTS
-#include "pgbart_spec.h"
-#include "pgbart_compiled.h"
-#define PGB_CL_EXPT pgb_tab_exp()
-#define PGB_CL_LOGT pgb_tab_log()
-#define PGB_CL_LPHI pgb_tab_lphi()
-#define PGB_COMPILED_VOCABULARY
-#include "pgbart_compiled.h"
-static double pgb_compiled_user(double y, const double* mu, double aux{params}) {{
-  enum {{ K = {K} }};
-{_body_text(body)}}}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-typedef struct {{
-  const double* aux;
-  double params[PGB_COMPILED_MAX_PARAMS];
-}} pgb_compiled_ctx;
-/* out[i] = the body at (y[i], mu[0 .. K-1][i] ([K][n]), aux[i] or 0.0), clamped like the sampler takes it */
-int pgb_compiled_eval_rows(void* ctx, const double* y, const double* mu, int64_t n, double* out) {{
-  const pgb_compiled_ctx* c = (const pgb_compiled_ctx*)ctx;
-  for (int64_t i = 0; i < n; ++i) {{
-    double m[{K}];
-    for (int k = 0; k < {K}; ++k) m[k] = mu[(size_t)k * (size_t)n + (size_t)i];
-    out[i] = pgb_clamp_loglik(pgb_compiled_user(y[i], m, c->aux ? c->aux[i] : 0.0{args}));
-  }}
-  return 0;
-}}
-"""
 
 
 def _compile_error(stderr: str, body: str, side: str, sampler: bool = False) -> CompileError:
@@ -406,18 +347,13 @@ def kernel_resources(code_object_path: str, kernel: str = "k_loglik_compiled") -
     raise CompileError(f"the code object has no kernel {kernel}")
 
 
-class CompiledLoglik:
-    """One build of a body: the code object (``code``), the host library (``host_lib``), the kernel's resource
-    usage (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit.  ``linear``: the code
-    object's pass kernel is the linear-leaf pass (a sampler with ``response="linear"`` / ``"mix"`` takes it, one with
-    constant leaves refuses it, and the other way round)."""
+class _Build:
+    """One build of a body: the code object (``code``), the host library (``host_lib``), the kernel's resource usage
+    (``resources``), the cache ``key``; ``compile_seconds`` is 0.0 on a cache hit."""
 
-    def __init__(self, key, body, param_names, max_particles, code, host_lib, resources, compile_seconds, cached,
-                 n_outputs=1, linear=False, pointwise=False):
-        self.key, self.body, self.param_names, self.max_particles = key, body, tuple(param_names), int(max_particles)
+    def __init__(self, key, body, param_names, code, host_lib, resources, compile_seconds, cached, n_outputs=1):
+        self.key, self.body, self.param_names = key, body, tuple(param_names)
         self.n_outputs = int(n_outputs)
-        self.linear = bool(linear)
-        self.pointwise = bool(pointwise)  # the code object holds k_pointwise_compiled instead of a pass kernel
         self.code, self.host_lib, self.resources = code, host_lib, resources
         self.compile_seconds, self.cached = compile_seconds, cached
         self._host = None
@@ -425,6 +361,23 @@ class CompiledLoglik:
     @property
     def n_params(self) -> int:
         return len(self.param_names)
+
+    def _host_fn(self, name: str, argtypes):
+        """The host build's entry point ``name`` as a ctypes function, loaded at its first use."""
+        if self._host is None:
+            self._host = getattr(C.CDLL(self.host_lib), name)
+            self._host.restype, self._host.argtypes = C.c_int, argtypes
+        return self._host
+
+
+class CompiledLoglik(_Build):
+    """The build of a density body.  ``linear``: the code object's pass kernel is the linear-leaf pass (a sampler with
+    ``response="linear"`` / ``"mix"`` takes it, one with constant leaves refuses it, and the other way round).
+    ``pointwise``: the code object holds ``k_pointwise_compiled`` instead of a pass kernel."""
+
+    def __init__(self, *args, max_particles=64, linear=False, pointwise=False):
+        super().__init__(*args)
+        self.max_particles, self.linear, self.pointwise = int(max_particles), bool(linear), bool(pointwise)
 
     def host_function(self):
         """The host build's ``pgb_compiled_loglik`` as a ctypes function (``pgb_loglik_fn``)."""
@@ -456,12 +409,9 @@ class CompiledLoglik:
             ctx.aux = keep.ctypes.data
         for i, v in enumerate(params):
             ctx.params[i] = float(v)
-        if self._host is None:
-            f = C.CDLL(self.host_lib).pgb_compiled_eval_rows
-            f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-            self._host = f
+        f = self._host_fn("pgb_compiled_eval_rows", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
         out = np.empty(n)
-        rc = self._host(C.cast(C.pointer(ctx), C.c_void_p), y.ctypes.data, mu.ctypes.data, n, out.ctypes.data)
+        rc = f(C.cast(C.pointer(ctx), C.c_void_p), y.ctypes.data, mu.ctypes.data, n, out.ctypes.data)
         if rc != 0:
             raise CompileError(f"pgb_compiled_eval_rows returned {rc}")
         return out
@@ -473,154 +423,8 @@ class CompiledContext(C.Structure):
     _fields_ = [("aux", C.c_void_p), ("params", C.c_double * MAX_PARAMS)]
 
 
-def _warn_scratch(b: "CompiledLoglik") -> None:
-    if b.pointwise:  # (the walk's own stack of the marginalising path lives in scratch: nothing about the body)
-        return
-    if (b.n_outputs > 1 or b.linear) and b.resources.get("scratch_bytes", 0) > 0:
-        warnings.warn(f"the likelihood body of {b.n_outputs} outputs{' (linear leaves)' if b.linear else ''} puts "
-                      f"{b.resources['scratch_bytes']} B per thread "
-                      "in scratch memory: mu lives in registers, and a run-time index such as mu[(int)y] moves it "
-                      "out.  Pick by comparison instead -- for (int k = 0; k < K; ++k) if (k == c) m = mu[k]; -- "
-                      "which is what the built-in softmax does", RuntimeWarning, stacklevel=3)
-
-
-def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1,
-                   linear: bool = False, pointwise: bool = False) -> CompiledLoglik:
-    """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
-    (64 or 128) and ``n_outputs`` predictors -- or take it from the cache.  ``linear``: the code object's pass is
-    the linear-leaf one (``response="linear"`` / ``"mix"``) instead of the constant-leaf one.  ``pointwise``: a code
-    object of its own kind -- no pass kernel but ``k_pointwise_compiled``, the body inside the posterior tree walk
-    (:mod:`pymc_bart_amd.pointwise`); it serves every kind of leaves and either particle build."""
-    K = check_outputs(n_outputs)
-    names = validate(body, param_names, K)
-    mp = 128 if int(max_particles) > 64 else 64
-    linear = bool(linear)
-    pointwise = bool(pointwise)
-    if pointwise:
-        if linear:
-            raise ValueError("pointwise=True takes no linear=True: the walk applies the leaves' slopes itself")
-        mp = 64  # (the kernel reads no particle record: one object for both builds)
-    key = cache_key(body, names, mp, K, linear, pointwise)
-    root = cache_dir()
-    os.makedirs(root, exist_ok=True)
-    co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
-    if os.path.exists(meta_path) and os.path.exists(co_path) and os.path.exists(so_path):
-        with open(meta_path) as fh:
-            meta = json.load(fh)
-        with open(co_path, "rb") as fh:
-            code = fh.read()
-        b = CompiledLoglik(key, body, names, mp, code, so_path, meta["resources"], 0.0, True, K, linear, pointwise)
-        _warn_scratch(b)
-        return b
-    t0 = time.perf_counter()
-    with tempfile.TemporaryDirectory(prefix="pgb_jit_") as tmp:
-        # host first: quick, and the compiler's messages about the body are the same on either side
-        src = os.path.join(tmp, "host.c")
-        with open(src, "w") as fh:
-            fh.write(_host_source(body, names, K))
-        so_tmp = os.path.join(tmp, "host.so")
-        r = subprocess.run(["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", src,
-                            "-o", so_tmp, "-lm"], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise _compile_error(r.stderr, body, "host")
-        with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
-            fh.write(_body_defs(names, mp, uses_tables(body), K, linear))
-        with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
-            fh.write(_body_text(body))
-        co_tmp = os.path.join(tmp, "k.co")
-        cmd = [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, f"-DPGB_MAX_PARTICLES={mp}", f"-I{CSRC}", f"-I{tmp}", "-w",
-               TU_POINTWISE if pointwise else TU, "-o", co_tmp]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise _compile_error(r.stderr, body, "device")
-        resources = kernel_resources(co_tmp, "k_pointwise_compiled" if pointwise else "k_loglik_compiled")
-        seconds = time.perf_counter() - t0
-        with open(co_tmp, "rb") as fh:
-            code = fh.read()
-        with open(so_tmp, "rb") as fh:
-            host = fh.read()
-    _write_atomic(co_path, code)
-    _write_atomic(so_path, host)
-    meta = {"body": body, "params": list(names), "max_particles": mp, "n_outputs": K, "linear": linear, "pointwise": pointwise,
-            "resources": resources,
-            "compile_seconds": seconds}
-    _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
-    b = CompiledLoglik(key, body, names, mp, code, so_path, resources, seconds, False, K, linear, pointwise)
-    _warn_scratch(b)
-    return b
-
-
-def _sampler_host_source(body: str, names, n_outputs: int = 1) -> str:
-    """The host build of a SAMPLER body: ``pgb_compiled_draw`` evaluates it over a ``[D][K][n]`` array of predictors
-    the way ``k_ppc_compiled`` does on the device -- the reference of every device test."""
-    params = "".join(f", const double {nm}" for nm in names)
-    args = "".join(f", prm[{i}]" for i in range(len(names)))
-    K = int(n_outputs)
-    mu_decl = "double mu" if K == 1 else "const double* mu"
-    k_enum = "" if K == 1 else f"  enum {{ K = {K} }};\n"
-    return f"""/* generated by pymc_bart_amd/compiled.py: the host build of a compiled likelihood's sampler body */
-#include <stdint.h>
-#include <stddef.h>
-#define PGB_COMPILED_NO_ENTRY_POINTS
-#include "pgbart_spec.h"
-#include "pgbart_compiled.h"
-#include "pgbart_ppc.h"
-#define PGB_CL_EXPT (pgb_cl_rng->tb->expt)
-#define PGB_CL_LOGT (pgb_cl_rng->tb->logt)
-#define PGB_CL_LPHI (pgb_cl_rng->tb->lphi)
-#define PGB_COMPILED_VOCABULARY
-#define PGB_COMPILED_SAMPLER_VOCABULARY
-#include "pgbart_compiled.h"
-static double pgb_compiled_sampler_user(pgb_ppc_ctx* pgb_cl_rng, {mu_decl}, double aux{params}) {{
-{k_enum}{_body_text(body, True)}}}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-/* out[D][n] (or NULL) of mu[D][K][n] at global rows row0 .. row0 + n; params[D][n_params]; aux[n] or NULL (0.0); y[n]
- * and pit[2][n] (added to) or NULL; flags[2] = (capped, exhausted) pairs */
-int pgb_compiled_draw(const double* mu, int D, int64_t n, uint64_t row0, const double* params, int n_params,
-                      const double* aux, uint64_t seed, double* out, const double* y, int32_t* pit, int64_t* flags) {{
-  const pgb_lltabs tb = pgb_lltabs_default();
-  flags[0] = flags[1] = 0;
-  for (int d = 0; d < D; ++d) {{
-    const double* prm = params + (size_t)d * (size_t)n_params;
-    for (int64_t i = 0; i < n; ++i) {{
-      double m[{K}];
-      for (int k = 0; k < {K}; ++k) m[k] = mu[((size_t)d * {K} + (size_t)k) * (size_t)n + (size_t)i];
-      pgb_ppc_ctx ctx;
-      uint32_t fl = 0;
-      pgb_ppc_ctx_begin(&ctx, seed, (uint32_t)d, row0 + (uint64_t)i, &tb);
-      const double v = pgb_ppc_ctx_end(&ctx, pgb_compiled_sampler_user(&ctx, {"m[0]" if K == 1 else "m"}, aux ? aux[i] : 0.0{args}), &fl);
-      if (fl & PGB_PPC_CAPPED) ++flags[0];
-      if (fl & PGB_PPC_EXHAUSTED) ++flags[1];
-      if (out) out[(size_t)d * (size_t)n + (size_t)i] = v;
-      if (y) {{
-        int below, equal;
-        pgb_ppc_compare(v, y[i], &below, &equal);
-        pit[i] += below;
-        pit[(size_t)n + (size_t)i] += equal;
-      }}
-    }}
-  }}
-  (void)n_params;
-  return 0;
-}}
-"""
-
-
-class CompiledSampler:
-    """One build of a SAMPLER body: the code object (``code``: ``k_ppc_compiled``, mark 2), the host library
-    (``host_lib``), the kernel's resource usage (``resources``), the cache ``key``."""
-
-    def __init__(self, key, body, param_names, code, host_lib, resources, compile_seconds, cached, n_outputs=1):
-        self.key, self.body, self.param_names = key, body, tuple(param_names)
-        self.n_outputs = int(n_outputs)
-        self.code, self.host_lib, self.resources = code, host_lib, resources
-        self.compile_seconds, self.cached = compile_seconds, cached
-        self._host = None
-
-    @property
-    def n_params(self) -> int:
-        return len(self.param_names)
+class CompiledSampler(_Build):
+    """The build of a SAMPLER body: the code object holds ``k_ppc_compiled`` (mark 2)."""
 
     def host_draw(self, mu, params=None, aux=None, seed=0, row0=0, y=None):
         """The host build of the body over ``mu`` ``(D, K, n)`` (the offset already added), ``params``
@@ -640,59 +444,56 @@ class CompiledSampler:
         yy = None if y is None else np.ascontiguousarray(y, np.float64).ravel()
         if yy is not None and yy.size != n:
             raise ValueError(f"y must hold n = {n} values")
-        if self._host is None:
-            f = C.CDLL(self.host_lib).pgb_compiled_draw
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
-                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            self._host = f
+        f = self._host_fn("pgb_compiled_draw", [C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
         out = np.empty((D, n))
         pit = None if yy is None else np.zeros((2, n), np.int32)
         flags = np.zeros(2, np.int64)
-        rc = self._host(mu.ctypes.data, D, n, int(row0), par.ctypes.data if par.size else None, self.n_params,
-                        None if ax is None else ax.ctypes.data, int(seed), out.ctypes.data,
-                        None if yy is None else yy.ctypes.data, None if pit is None else pit.ctypes.data, flags.ctypes.data)
+        rc = f(mu.ctypes.data, D, n, int(row0), par.ctypes.data if par.size else None, self.n_params,
+               None if ax is None else ax.ctypes.data, int(seed), out.ctypes.data,
+               None if yy is None else yy.ctypes.data, None if pit is None else pit.ctypes.data, flags.ctypes.data)
         if rc != 0:
             raise CompileError(f"pgb_compiled_draw returned {rc}")
         return out, pit, (int(flags[0]), int(flags[1]))
 
 
-def compile_sampler(body: str, param_names=(), n_outputs: int = 1) -> CompiledSampler:
-    """Compile the SAMPLER body ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) of ``n_outputs`` predictors
-    into ``k_ppc_compiled`` (``csrc/k_ppc_compiled.hip``) and its host evaluator -- or take them from the cache.  The
-    kernel reads no particle record: one object serves both particle builds."""
-    K = check_outputs(n_outputs)
-    names = validate(body, param_names, K, sampler=True)
-    key = cache_key(body, names, 64, K, sampler=True)
+def _build(kind: str, body: str, names, mp: int = 64, K: int = 1, linear: bool = False):
+    """The one build path of every kind of ``_KINDS``: the cache entry of the key, or -- in a temporary directory --
+    the two generated files, the host build (first: quick, and the compiler's messages about the body are the same on
+    either side), the device build and its kernel's resources; then the entry's three files, written atomically."""
+    (device, host_unit, kernel, defines), sampler, pointwise = _KINDS[kind], kind == "sampler", kind == "pointwise"
+    key = cache_key(body, names, mp, K, linear, pointwise, sampler)
     root = cache_dir()
     os.makedirs(root, exist_ok=True)
     co_path, so_path, meta_path = (os.path.join(root, key + ext) for ext in (".co", ".so", ".json"))
+
+    def result(code, resources, seconds, cached):
+        if sampler:
+            return CompiledSampler(key, body, names, code, so_path, resources, seconds, cached, K)
+        return CompiledLoglik(key, body, names, code, so_path, resources, seconds, cached, K,
+                              max_particles=mp, linear=linear, pointwise=pointwise)
+
     if os.path.exists(meta_path) and os.path.exists(co_path) and os.path.exists(so_path):
         with open(meta_path) as fh:
             meta = json.load(fh)
         with open(co_path, "rb") as fh:
-            code = fh.read()
-        return CompiledSampler(key, body, names, code, so_path, meta["resources"], 0.0, True, K)
+            return result(fh.read(), meta["resources"], 0.0, True)
     t0 = time.perf_counter()
     with tempfile.TemporaryDirectory(prefix="pgb_jit_") as tmp:
-        src = os.path.join(tmp, "host.c")
-        with open(src, "w") as fh:
-            fh.write(_sampler_host_source(body, names, K))
-        so_tmp = os.path.join(tmp, "host.so")
-        r = subprocess.run(["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", src,
-                            "-o", so_tmp, "-lm"], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise _compile_error(r.stderr, body, "host", sampler=True)
         with open(os.path.join(tmp, "pgb_compiled_body.inc"), "w") as fh:
-            fh.write(_body_defs(names, 64, False, K))
+            fh.write(_body_defs(names, not sampler and uses_tables(body), K, linear))
         with open(os.path.join(tmp, "pgb_compiled_body_text.inc"), "w") as fh:
-            fh.write(_body_text(body, True))
-        co_tmp = os.path.join(tmp, "k.co")
-        cmd = [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, f"-I{CSRC}", f"-I{tmp}", "-w", TU_SAMPLER, "-o", co_tmp]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise _compile_error(r.stderr, body, "device", sampler=True)
-        resources = kernel_resources(co_tmp, "k_ppc_compiled")
+            fh.write(_body_text(body, sampler))
+        so_tmp, co_tmp = os.path.join(tmp, "host.so"), os.path.join(tmp, "k.co")
+        for side, cmd in (
+                ("host", ["gcc", *HOST_FLAGS, "-Werror=implicit-function-declaration", f"-I{INCLUDE}", f"-I{tmp}",
+                          os.path.join(CSRC, host_unit), "-o", so_tmp, "-lm"]),
+                ("device", [hipcc_path(), *DEVICE_FLAGS, *GENCO_FLAGS, *(d.format(mp=mp) for d in defines),
+                            f"-I{CSRC}", f"-I{tmp}", "-w", os.path.join(CSRC, device), "-o", co_tmp])):
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise _compile_error(r.stderr, body, side, sampler)
+        resources = kernel_resources(co_tmp, kernel)
         seconds = time.perf_counter() - t0
         with open(co_tmp, "rb") as fh:
             code = fh.read()
@@ -700,9 +501,47 @@ def compile_sampler(body: str, param_names=(), n_outputs: int = 1) -> CompiledSa
             host = fh.read()
     _write_atomic(co_path, code)
     _write_atomic(so_path, host)
-    meta = {"sampler": body, "params": list(names), "n_outputs": K, "resources": resources, "compile_seconds": seconds}
+    meta = {"sampler": body} if sampler else {"body": body, "max_particles": mp, "linear": linear, "pointwise": pointwise}
+    meta.update(params=list(names), n_outputs=K, resources=resources, compile_seconds=seconds)
     _write_atomic(meta_path, json.dumps(meta, indent=1).encode())  # (last: an entry is complete once it exists)
-    return CompiledSampler(key, body, names, code, so_path, resources, seconds, False, K)
+    return result(code, resources, seconds, False)
+
+
+def _warn_scratch(b: CompiledLoglik) -> None:
+    if b.pointwise:  # (the walk's own stack of the marginalising path lives in scratch: nothing about the body)
+        return
+    if (b.n_outputs > 1 or b.linear) and b.resources.get("scratch_bytes", 0) > 0:
+        warnings.warn(f"the likelihood body of {b.n_outputs} outputs{' (linear leaves)' if b.linear else ''} puts "
+                      f"{b.resources['scratch_bytes']} B per thread "
+                      "in scratch memory: mu lives in registers, and a run-time index such as mu[(int)y] moves it "
+                      "out.  Pick by comparison instead -- for (int k = 0; k < K; ++k) if (k == c) m = mu[k]; -- "
+                      "which is what the built-in softmax does", RuntimeWarning, stacklevel=3)
+
+
+def compile_loglik(body: str, param_names=(), max_particles: int = 64, n_outputs: int = 1,
+                   linear: bool = False, pointwise: bool = False) -> CompiledLoglik:
+    """Compile ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) for the particle build ``max_particles``
+    (64 or 128) and ``n_outputs`` predictors -- or take it from the cache.  ``linear``: the code object's pass is
+    the linear-leaf one (``response="linear"`` / ``"mix"``) instead of the constant-leaf one.  ``pointwise``: a code
+    object of its own kind -- no pass kernel but ``k_pointwise_compiled``, the body inside the posterior tree walk
+    (:mod:`pymc_bart_amd.pointwise`); it serves every kind of leaves and either particle build."""
+    K = check_outputs(n_outputs)
+    names = validate(body, param_names, K)
+    if pointwise and linear:
+        raise ValueError("pointwise=True takes no linear=True: the walk applies the leaves' slopes itself")
+    # (the pointwise kernel reads no particle record: one object for both builds)
+    mp = 128 if int(max_particles) > 64 and not pointwise else 64
+    b = _build("pointwise" if pointwise else "pass", body, names, mp, K, bool(linear))
+    _warn_scratch(b)
+    return b
+
+
+def compile_sampler(body: str, param_names=(), n_outputs: int = 1) -> CompiledSampler:
+    """Compile the SAMPLER body ``body`` (see :class:`pymc_bart_amd.CompiledLikelihood`) of ``n_outputs`` predictors
+    into ``k_ppc_compiled`` (``csrc/k_ppc_compiled.hip``) and its host evaluator -- or take them from the cache.  The
+    kernel reads no particle record: one object serves both particle builds."""
+    K = check_outputs(n_outputs)
+    return _build("sampler", body, validate(body, param_names, K, sampler=True), K=K)
 
 
 class CompiledLikelihood:

@@ -1,22 +1,17 @@
-// k_loglik_compiled.hip -- the code object of the compiled likelihood family (include/pgbart_compiled.h).
+// k_loglik_compiled.hip -- the PASS code object of the compiled likelihood family (include/pgbart_compiled.h).
 //
 // Not part of libpgbart_hip.so: pymc_bart_amd/compiled.py compiles this unit at run time with the library's device
-// flags plus --genco, once per (body, param names, outputs, particle build), next to two generated files in its
-// build directory:
-//   pgb_compiled_body.inc       PGB_COMPILED_PARAMS (", const double <name>" per param), PGB_COMPILED_ARGS(P)
-//                               (", (P).v[i]" per param), PGB_COMPILED_NPARAMS, PGB_COMPILED_NOUT (K),
-//                               PGB_COMPILED_LINEAR (0: constant leaves, 1: linear leaves), PGB_COMPILED_EXPLOG,
-//                               PGB_HEADERS_HASH
-//   pgb_compiled_body_text.inc  the user's body, behind a #line directive (compiler messages quote the user's lines)
-// The kernel is the library's constant-leaf pass with the generated function at every place where the family is
-// evaluated: k_loglik<1, PGB_FAMILY_COMPILED, false> (plain, not dense, path) for one output; for K outputs the
-// K-vector pass of the same K as the built-in families -- k_loglik<K> for K = 2, 3, 4 (loops unrolled), k_loglik<0>
-// (run-time K) above -- at the built-in instance's occupancy.  With PGB_COMPILED_LINEAR the ONE pass kernel of the
-// code object is the linear-leaf pass instead (response linear / mix): k_loglik<1, PGB_FAMILY_COMPILED, true> for one
-// output, k_loglik<0, PGB_FAMILY_COMPILED, true> -- the run-time-K linear path with the K predictors of a row in an
-// array of K doubles -- for K outputs, at the launch bounds of the built-in linear instances.  Next to it: the layout record the library checks
-// before the first launch (pgb_set_loglik_code), and a probe kernel that evaluates the body on given rows
-// (pgb_compiled_probe).
+// flags plus --genco, once per (body, param names, outputs, particle build, leaves); the body becomes
+// pgb_compiled_user in include/pgbart_compiled_body.h, which also describes the two generated files.
+// The kernel is the library's constant-leaf pass with that function at every place where the family is evaluated:
+// k_loglik<1, PGB_FAMILY_COMPILED, false> (plain, not dense, path) for one output; for K outputs the K-vector pass of
+// the same K as the built-in families -- k_loglik<K> for K = 2, 3, 4 (loops unrolled), k_loglik<0> (run-time K) above
+// -- at the built-in instance's occupancy.  With PGB_COMPILED_LINEAR the ONE pass kernel of the code object is the
+// linear-leaf pass instead (response linear / mix): k_loglik<1, PGB_FAMILY_COMPILED, true> for one output,
+// k_loglik<0, PGB_FAMILY_COMPILED, true> -- the run-time-K linear path with the K predictors of a row in an array of
+// K doubles -- for K outputs, at the launch bounds of the built-in linear instances.  Next to it: the layout record
+// the library checks before the first launch (pgb_set_loglik_code), and a probe kernel that evaluates the body on
+// given rows (pgb_compiled_probe).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -30,13 +25,6 @@
 
 #include "pgb_dims.h"
 #include "pgb_compiled_body.inc"
-#ifndef PGB_COMPILED_NOUT
-#define PGB_COMPILED_NOUT 1
-#endif
-#if PGB_COMPILED_NOUT < 1 || PGB_COMPILED_NOUT > PGB_MAX_OUTPUTS
-#error "PGB_COMPILED_NOUT must be in [1, PGB_MAX_OUTPUTS]"
-#endif
-
 #ifndef PGB_COMPILED_LINEAR
 #define PGB_COMPILED_LINEAR 0
 #endif
@@ -50,29 +38,9 @@
 #include "pgb_leaf_values.h"
 #include "k_ctrl.h"
 
-// ---- the body, with the vocabulary on (exp / log on the tables the kernel passes: its LDS copies)
-#define PGB_CL_EXPT (pgb_cl_tb->expt)
-#define PGB_CL_LOGT (pgb_cl_tb->logt)
-#define PGB_CL_LPHI (pgb_cl_tb->lphi)
-#define PGB_COMPILED_VOCABULARY
-#include "pgbart_compiled.h"
-#if PGB_COMPILED_NOUT == 1
-typedef double pgb_compiled_mu;
-#else
-typedef const double* pgb_compiled_mu;  // (the kernel's register array of the K predictors)
-#endif
-__device__ __forceinline__ double pgb_compiled_user(const pgb_lltabs* __restrict__ pgb_cl_tb, double y,
-                                                    pgb_compiled_mu mu, double aux PGB_COMPILED_PARAMS) {
-#if PGB_COMPILED_NOUT > 1
-  enum { K = PGB_COMPILED_NOUT };
-#endif
-#include "pgb_compiled_body_text.inc"
-}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-#undef PGB_CL_EXPT
-#undef PGB_CL_LOGT
-#undef PGB_CL_LPHI
+// ---- the body (its tables: the ones the kernel passes, its LDS copies)
+#define PGB_COMPILED_BODY_QUAL __device__ __forceinline__
+#include "pgbart_compiled_body.h"
 
 // the per-row value as the callback family takes it: clamped to [-2047, 2047], NaN -> -2047 (pgb_clamp_loglik)
 __device__ __forceinline__ double pgb_compiled_eval(double y, pgb_compiled_mu mu, double aux,

@@ -2,8 +2,8 @@
 // include/pgbart_pointwise.h).
 //
 // Not part of libpgbart_hip.so: pymc_bart_amd/compiled.py compiles this unit at run time (compile_loglik(...,
-// pointwise=True)) with the library's device flags plus --genco, next to the two generated files k_loglik_compiled.hip
-// documents (pgb_compiled_body.inc, pgb_compiled_body_text.inc).  The code object holds ONE kernel,
+// pointwise=True)) with the library's device flags plus --genco; the body becomes pgb_compiled_user in
+// include/pgbart_compiled_body.h, which also describes the two generated files.  The code object holds ONE kernel,
 // k_pointwise_compiled: the library's k_pointwise (k_pointwise.h: k_predict's walk, the per (draw, row) epilogue, the
 // fold over draws) with the user's body at the evaluation site -- mu a scalar or the register array of the K
 // predictors, aux read next to y, the draw's params from the parameter table, the clamp of pgb_compiled_eval -- for
@@ -22,36 +22,10 @@
 
 #include "pgb_dims.h"
 #include "pgb_compiled_body.inc"
-#ifndef PGB_COMPILED_NOUT
-#define PGB_COMPILED_NOUT 1
-#endif
-#if PGB_COMPILED_NOUT < 1 || PGB_COMPILED_NOUT > PGB_MAX_OUTPUTS
-#error "PGB_COMPILED_NOUT must be in [1, PGB_MAX_OUTPUTS]"
-#endif
 
-// ---- the body, with the vocabulary on (the tables: global memory, as the probe kernel reads them)
-#define PGB_CL_EXPT (pgb_cl_tb->expt)
-#define PGB_CL_LOGT (pgb_cl_tb->logt)
-#define PGB_CL_LPHI (pgb_cl_tb->lphi)
-#define PGB_COMPILED_VOCABULARY
-#include "pgbart_compiled.h"
-#if PGB_COMPILED_NOUT == 1
-typedef double pgb_compiled_mu;
-#else
-typedef const double* pgb_compiled_mu;  // (the kernel's register array of the K predictors)
-#endif
-__device__ __forceinline__ double pgb_compiled_user(const pgb_lltabs* __restrict__ pgb_cl_tb, double y,
-                                                    pgb_compiled_mu mu, double aux PGB_COMPILED_PARAMS) {
-#if PGB_COMPILED_NOUT > 1
-  enum { K = PGB_COMPILED_NOUT };
-#endif
-#include "pgb_compiled_body_text.inc"
-}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-#undef PGB_CL_EXPT
-#undef PGB_CL_LOGT
-#undef PGB_CL_LPHI
+// ---- the body (its tables: global memory, as the probe kernel reads them)
+#define PGB_COMPILED_BODY_QUAL __device__ __forceinline__
+#include "pgbart_compiled_body.h"
 
 #define PGB_PW_COMPILED 1
 #include "pgb_pred_walk.h"

@@ -2,9 +2,8 @@
 // include/pgbart_ppc.h).
 //
 // Not part of libpgbart_hip.so: pymc_bart_amd/compiled.py compiles this unit at run time (compile_sampler) with the
-// library's device flags plus --genco, next to the two generated files k_loglik_compiled.hip documents
-// (pgb_compiled_body.inc, pgb_compiled_body_text.inc -- here the text of the likelihood's sampler body).  The code
-// object holds ONE kernel, k_ppc_compiled: the library's k_ppc (k_ppc.h: one thread per row, 256 rows per workgroup,
+// library's device flags plus --genco; the likelihood's sampler body becomes pgb_compiled_sampler_user in
+// include/pgbart_compiled_body.h, which also describes the two generated files.  The code object holds ONE kernel, k_ppc_compiled: the library's k_ppc (k_ppc.h: one thread per row, 256 rows per workgroup,
 // chunks of PGB_PW_CHUNK draws on grid y, the PIT fold, the ballot / popcount flag counts, the in-place rule) with the
 // user's sampler body at the evaluation site -- mu a scalar or the register array of the K predictors, aux read next to
 // the row, the draw's params from the [D][PGB_COMPILED_MAX_PARAMS] table, the random vocabulary on a pgb_ppc_ctx of
@@ -24,37 +23,11 @@
 
 #include "pgb_dims.h"
 #include "pgb_compiled_body.inc"
-#ifndef PGB_COMPILED_NOUT
-#define PGB_COMPILED_NOUT 1
-#endif
-#if PGB_COMPILED_NOUT < 1 || PGB_COMPILED_NOUT > PGB_MAX_OUTPUTS
-#error "PGB_COMPILED_NOUT must be in [1, PGB_MAX_OUTPUTS]"
-#endif
 
-// ---- the sampler body, with both vocabularies on (the tables: global memory, as k_ppc reads them)
-#define PGB_CL_EXPT (pgb_cl_rng->tb->expt)
-#define PGB_CL_LOGT (pgb_cl_rng->tb->logt)
-#define PGB_CL_LPHI (pgb_cl_rng->tb->lphi)
-#define PGB_COMPILED_VOCABULARY
-#define PGB_COMPILED_SAMPLER_VOCABULARY
-#include "pgbart_compiled.h"
-#if PGB_COMPILED_NOUT == 1
-typedef double pgb_compiled_mu;
-#else
-typedef const double* pgb_compiled_mu;  // (the kernel's register array of the K predictors)
-#endif
-__device__ __forceinline__ double pgb_compiled_sampler_user(pgb_ppc_ctx* __restrict__ pgb_cl_rng, pgb_compiled_mu mu,
-                                                            double aux PGB_COMPILED_PARAMS) {
-#if PGB_COMPILED_NOUT > 1
-  enum { K = PGB_COMPILED_NOUT };
-#endif
-#include "pgb_compiled_body_text.inc"
-}
-#define PGB_COMPILED_VOCABULARY_END
-#include "pgbart_compiled.h"
-#undef PGB_CL_EXPT
-#undef PGB_CL_LOGT
-#undef PGB_CL_LPHI
+// ---- the sampler body, with both vocabularies on (its tables: global memory, as k_ppc reads them)
+#define PGB_COMPILED_BODY_QUAL __device__ __forceinline__
+#define PGB_COMPILED_BODY_SAMPLER
+#include "pgbart_compiled_body.h"
 
 #define PGB_PPC_COMPILED 1
 #include "k_ppc.h"

@@ -1,6 +1,7 @@
 // pgb_compiled_host.h -- part of pgbart_hip.hip (not a standalone header): host side of the compiled likelihood family
-// (include/pgbart_compiled.h): loading and checking a code object built from k_loglik_compiled.hip, its params,
-// its aux column, its launch.  Included by pgb_host.h after the launch helpers.
+// (include/pgbart_compiled.h): the one loader of a compiled code object of any kind (compiled_load_code; its callers
+// pgb_set_loglik_code here, pgb_pointwise_loglik, pgb_ppc_draw_compiled), and a pass object's params, aux column and
+// launch.  Included by pgb_host.h after the launch helpers.
 #ifndef PGB_HEADERS_HASH
 #define PGB_HEADERS_HASH 0ull  // (a build without the hash -- __graft_entry__.build passes it -- refuses every code object)
 #endif
@@ -11,73 +12,133 @@ static void compiled_size_grid(pgb_handle* h) {
   if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->cl_fn, BT, 0) == hipSuccess) size_ll_grid(h, per_cu);
 }
 
+// what a layout record's mark says the code object is (the words follow "one")
+static const char* compiled_mark_name(int mark) {
+  return mark == PGB_COMPILED_MARK_PASS        ? "built without pointwise=True (a sampler's pass kernel, " PGB_COMPILED_KERNEL ")"
+         : mark == PGB_COMPILED_MARK_POINTWISE ? "built with pointwise=True (" PGB_POINTWISE_KERNEL ")"
+         : mark == PGB_COMPILED_MARK_SAMPLER   ? "built from a sampler body (" PGB_PPC_COMPILED_KERNEL ")"
+                                               : "of an unknown kind";
+}
+
+// The ONE loader of a compiled body's code object, for `entry` (pgb_set_loglik_code: mark 0, pgb_pointwise_loglik:
+// mark 1, pgb_ppc_draw_compiled: mark 2): loaded into *mod (the caller unloads it, on every way out), its layout
+// record -- left in *rec -- held against the call's, the mark's kernel looked up; never launched when they differ
+// (the message names both sides).  k_side: how the call's K reads in a message.
+static int compiled_load_code(const void* code_object, int64_t code_bytes, int n_params, int K, const char* k_side,
+                              int want_mark, const char* entry, hipModule_t* mod, hipFunction_t* fn,
+                              pgb_compiled_layout* rec) {
+  if (!code_object || code_bytes < 64) return fail(PGB_E_INVALID, "the compiled family needs a code object");
+  // only an ELF object goes to the loader (the runtime parses what it is given; anything else is refused here)
+  const unsigned char* b = (const unsigned char*)code_object;
+  if (!(b[0] == 0x7f && b[1] == 'E' && b[2] == 'L' && b[3] == 'F'))
+    return fail(PGB_E_INVALID, "not a gfx950 code object (no ELF header): compile it with pymc_bart_amd.compiled");
+  hipError_t e = hipModuleLoadData(mod, code_object);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *mod = nullptr;
+    snprintf(g_err, sizeof g_err, "the code object does not load: %s", hipGetErrorString(e));
+    return PGB_E_INVALID;
+  }
+  memset(rec, 0, sizeof *rec);
+  hipDeviceptr_t gp = nullptr;
+  size_t gbytes = 0;
+  if (hipModuleGetGlobal(&gp, &gbytes, *mod, PGB_COMPILED_LAYOUT) != hipSuccess || gbytes != sizeof *rec) {
+    (void)hipGetLastError();
+    return fail(PGB_E_INVALID, "the code object has no layout record " PGB_COMPILED_LAYOUT);
+  }
+  HIPCHK(hipMemcpyDtoH(rec, gp, sizeof *rec));
+  if (rec->magic != PGB_COMPILED_MAGIC) return fail(PGB_E_INVALID, "the layout record is not one of a compiled likelihood");
+  if (rec->pointwise != want_mark) {
+    snprintf(g_err, sizeof g_err, "the code object is one %s, mark %d: %s takes one %s", compiled_mark_name(rec->pointwise),
+             (int)rec->pointwise, entry, compiled_mark_name(want_mark));
+    return PGB_E_INVALID;
+  }
+  if (PGB_HEADERS_HASH == 0ull || rec->headers_hash != (uint64_t)PGB_HEADERS_HASH) {
+    snprintf(g_err, sizeof g_err, "the code object was compiled from other kernel headers (hash %016llx) than this library "
+             "(%016llx)", (unsigned long long)rec->headers_hash, (unsigned long long)PGB_HEADERS_HASH);
+    return PGB_E_INVALID;
+  }
+  if (rec->n_params != n_params) {
+    snprintf(g_err, sizeof g_err, "the code object was compiled for %d params, the call gives n_params = %d",
+             (int)rec->n_params, n_params);
+    return PGB_E_INVALID;
+  }
+  if (rec->n_outputs != K) {
+    snprintf(g_err, sizeof g_err, "the code object was compiled for %d outputs, %s = %d", (int)rec->n_outputs, k_side, K);
+    return PGB_E_INVALID;
+  }
+  const char* kernel = want_mark == PGB_COMPILED_MARK_SAMPLER     ? PGB_PPC_COMPILED_KERNEL
+                       : want_mark == PGB_COMPILED_MARK_POINTWISE ? PGB_POINTWISE_KERNEL
+                                                                  : PGB_COMPILED_KERNEL;
+  if (hipModuleGetFunction(fn, *mod, kernel) != hipSuccess) {
+    (void)hipGetLastError();
+    snprintf(g_err, sizeof g_err, "the code object has no kernel %s", kernel);
+    return PGB_E_INVALID;
+  }
+  return PGB_OK;
+}
+
+// the draws' params ([D][n_params], host) as the table [D][PGB_COMPILED_MAX_PARAMS] a pointwise or sampler kernel
+// reads (dst: zeroed by the caller); false at the first non-finite one, whose place *bad_d, *bad_i give (each caller
+// has its own sentence)
+static bool compiled_params_table(const double* src, int D, int n_params, double* dst, int* bad_d, int* bad_i) {
+  for (int d = 0; d < D; ++d)
+    for (int i = 0; i < n_params; ++i) {
+      const double v = src[(size_t)d * n_params + i];
+      if (!(v - v == 0.0)) {
+        *bad_d = d, *bad_i = i;
+        return false;
+      }
+      dst[(size_t)d * PGB_COMPILED_MAX_PARAMS + i] = v;
+    }
+  return true;
+}
+
+// the checks of a PASS object alone, after the shared ones: nullptr, or why the sampler cannot run it (why_k: room for
+// a sentence with both sides in it)
+static const char* compiled_pass_refusal(const pgb_handle* h, const pgb_compiled_layout& rec, char (&why_k)[128]) {
+  if (rec.max_particles != PGB_MAX_PARTICLES)
+    return "the code object was built for another particle build (this library takes " PGB_STR(PGB_MAX_PARTICLES) ")";
+  if (rec.sizeof_dev != (int64_t)sizeof(Dev) || rec.sizeof_job != (int64_t)sizeof(Job) ||
+      rec.sizeof_cmd != (int64_t)sizeof(Cmd) || rec.sizeof_ctrl != (int64_t)sizeof(Ctrl) ||
+      rec.sizeof_acc != (int64_t)sizeof(Acc))
+    return "the code object's device records differ from this library's";
+  if ((rec.linear_leaves != 0) != (h->s.response != PGB_RESPONSE_CONSTANT) ||
+      (rec.linear_leaves != 0 && rec.linear_leaves != 1)) {
+    const char* resp = h->s.response == PGB_RESPONSE_CONSTANT ? "constant"
+                       : h->s.response == PGB_RESPONSE_LINEAR ? "linear" : "mix";
+    snprintf(why_k, sizeof why_k, "the code object was compiled for %s leaves, the sampler has response = %s",
+             rec.linear_leaves == 0 ? "constant" : rec.linear_leaves == 1 ? "linear" : "unknown", resp);
+    return why_k;
+  }
+  return nullptr;
+}
+
 extern "C" int pgb_set_loglik_code(pgb_handle* h, const void* code_object, int64_t bytes, int32_t n_params) {
   if (!h) return fail(PGB_E_INVALID, "null handle");
   JOIN_ASYNC(h);
   if (h->s.family != PGB_FAMILY_COMPILED)
     return fail(PGB_E_INVALID, "the sampler was not created with the compiled family");
-  if (!code_object || bytes < 64) return fail(PGB_E_INVALID, "no code object");
   if (n_params < 0 || n_params > PGB_COMPILED_MAX_PARAMS)
     return fail(PGB_E_INVALID, "n_params must be in [0, " PGB_STR(PGB_COMPILED_MAX_PARAMS) "]");
-  // only an ELF object goes to the loader (the runtime parses what it is given; anything else is refused here)
-  const unsigned char* b = (const unsigned char*)code_object;
-  if (!(b[0] == 0x7f && b[1] == 'E' && b[2] == 'L' && b[3] == 'F'))
-    return fail(PGB_E_INVALID, "not a gfx950 code object (no ELF header): compile it with pymc_bart_amd.compiled");
+  // a refused object is never launched and never replaces the loaded one: the handle is untouched until every check
+  // has passed
   hipModule_t mod = nullptr;
-  hipError_t e = hipModuleLoadData(&mod, code_object);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    snprintf(g_err, sizeof g_err, "the code object does not load: %s", hipGetErrorString(e));
-    return PGB_E_INVALID;
-  }
-  // the layout record: read, never launched
-  const char* why = nullptr;
-  char why_k[128];
-  pgb_compiled_layout rec;
-  memset(&rec, 0, sizeof rec);
-  hipDeviceptr_t gp = nullptr;
-  size_t gbytes = 0;
-  if (hipModuleGetGlobal(&gp, &gbytes, mod, PGB_COMPILED_LAYOUT) != hipSuccess || gbytes != sizeof rec)
-    why = "the code object has no layout record " PGB_COMPILED_LAYOUT;
-  else if (hipMemcpyDtoH(&rec, gp, sizeof rec) != hipSuccess)
-    why = "the layout record could not be read";
-  else if (rec.magic != PGB_COMPILED_MAGIC)
-    why = "the layout record is not one of a compiled likelihood";
-  else if (rec.pointwise == PGB_COMPILED_MARK_SAMPLER)
-    why = "the code object is one built from a sampler body (" PGB_PPC_COMPILED_KERNEL ", mark 2): pgb_set_loglik_code "
-          "takes a sampler's pass kernel";
-  else if (rec.max_particles != PGB_MAX_PARTICLES)
-    why = PGB_MAX_PARTICLES == 64 ? "the code object was built for another particle build (this library takes 64)"
-                                  : "the code object was built for another particle build (this library takes 128)";
-  else if (rec.sizeof_dev != (int64_t)sizeof(Dev) || rec.sizeof_job != (int64_t)sizeof(Job) ||
-           rec.sizeof_cmd != (int64_t)sizeof(Cmd) || rec.sizeof_ctrl != (int64_t)sizeof(Ctrl) ||
-           rec.sizeof_acc != (int64_t)sizeof(Acc))
-    why = "the code object's device records differ from this library's";
-  else if (PGB_HEADERS_HASH == 0ull || rec.headers_hash != (uint64_t)PGB_HEADERS_HASH)
-    why = "the code object was compiled from other kernel headers than this library";
-  else if (rec.n_params != n_params)
-    why = "n_params differs from the params the code object was compiled for";
-  else if (rec.n_outputs != h->s.n_outputs) {
-    snprintf(why_k, sizeof why_k, "the code object was compiled for %d outputs, the sampler has n_outputs = %d",
-             (int)rec.n_outputs, (int)h->s.n_outputs);
-    why = why_k;
-  } else if ((rec.linear_leaves != 0) != (h->s.response != PGB_RESPONSE_CONSTANT) ||
-             (rec.linear_leaves != 0 && rec.linear_leaves != 1)) {
-    const char* resp = h->s.response == PGB_RESPONSE_CONSTANT ? "constant"
-                       : h->s.response == PGB_RESPONSE_LINEAR ? "linear" : "mix";
-    snprintf(why_k, sizeof why_k, "the code object was compiled for %s leaves, the sampler has response = %s",
-             rec.linear_leaves == 0 ? "constant" : rec.linear_leaves == 1 ? "linear" : "unknown", resp);
-    why = why_k;
-  }
   hipFunction_t fn = nullptr, probe = nullptr;
-  if (!why && hipModuleGetFunction(&fn, mod, PGB_COMPILED_KERNEL) != hipSuccess)
-    why = "the code object has no kernel " PGB_COMPILED_KERNEL;
-  if (!why && hipModuleGetFunction(&probe, mod, PGB_COMPILED_PROBE) != hipSuccess)
-    why = "the code object has no kernel " PGB_COMPILED_PROBE;
-  if (why) {
+  pgb_compiled_layout rec;
+  char why_k[128];
+  int rc = compiled_load_code(code_object, bytes, n_params, h->s.n_outputs, "the sampler has n_outputs",
+                              PGB_COMPILED_MARK_PASS, "pgb_set_loglik_code", &mod, &fn, &rec);
+  if (rc == PGB_OK) {
+    const char* why = compiled_pass_refusal(h, rec, why_k);
+    if (!why && hipModuleGetFunction(&probe, mod, PGB_COMPILED_PROBE) != hipSuccess)
+      why = "the code object has no kernel " PGB_COMPILED_PROBE;
+    if (why) rc = fail(PGB_E_INVALID, why);
+  }
+  if (rc != PGB_OK) {
     (void)hipGetLastError();
-    (void)hipModuleUnload(mod);
-    return fail(PGB_E_INVALID, why);
+    if (mod) (void)hipModuleUnload(mod);
+    return rc;
   }
   // replace the old module: nothing queued may still run it
   HIPCHK(hipStreamSynchronize(h->stream));

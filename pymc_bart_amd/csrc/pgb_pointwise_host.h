@@ -16,68 +16,6 @@ struct PwScratch {
   }
 };
 
-// what a layout record's mark says the code object is (the words follow "one")
-static const char* compiled_mark_name(int mark) {
-  return mark == PGB_COMPILED_MARK_PASS        ? "built without pointwise=True (a sampler's pass kernel, " PGB_COMPILED_KERNEL ")"
-         : mark == PGB_COMPILED_MARK_POINTWISE ? "built with pointwise=True (" PGB_POINTWISE_KERNEL ")"
-         : mark == PGB_COMPILED_MARK_SAMPLER   ? "built from a sampler body (" PGB_PPC_COMPILED_KERNEL ")"
-                                               : "of an unknown kind";
-}
-
-// the code object of a compiled body for one call of `entry` (pgb_pointwise_loglik: mark 1, pgb_ppc_draw_compiled:
-// mark 2): loaded into *mod (the caller unloads it), its layout record held against the call's, never launched when
-// they differ (the message names both sides).  k_side: how the call's K reads in a message.
-static int compiled_load_code(const void* code_object, int64_t code_bytes, int n_params, int K, const char* k_side,
-                              int want_mark, const char* entry, hipModule_t* mod, hipFunction_t* fn) {
-  if (!code_object || code_bytes < 64) return fail(PGB_E_INVALID, "the compiled family needs a code object");
-  const unsigned char* b = (const unsigned char*)code_object;
-  if (!(b[0] == 0x7f && b[1] == 'E' && b[2] == 'L' && b[3] == 'F'))
-    return fail(PGB_E_INVALID, "not a gfx950 code object (no ELF header): compile it with pymc_bart_amd.compiled");
-  hipError_t e = hipModuleLoadData(mod, code_object);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *mod = nullptr;
-    snprintf(g_err, sizeof g_err, "the code object does not load: %s", hipGetErrorString(e));
-    return PGB_E_INVALID;
-  }
-  pgb_compiled_layout rec;
-  memset(&rec, 0, sizeof rec);
-  hipDeviceptr_t gp = nullptr;
-  size_t gbytes = 0;
-  if (hipModuleGetGlobal(&gp, &gbytes, *mod, PGB_COMPILED_LAYOUT) != hipSuccess || gbytes != sizeof rec) {
-    (void)hipGetLastError();
-    return fail(PGB_E_INVALID, "the code object has no layout record " PGB_COMPILED_LAYOUT);
-  }
-  HIPCHK(hipMemcpyDtoH(&rec, gp, sizeof rec));
-  if (rec.magic != PGB_COMPILED_MAGIC) return fail(PGB_E_INVALID, "the layout record is not one of a compiled likelihood");
-  if (rec.pointwise != want_mark) {
-    snprintf(g_err, sizeof g_err, "the code object is one %s, mark %d: %s takes one %s", compiled_mark_name(rec.pointwise),
-             (int)rec.pointwise, entry, compiled_mark_name(want_mark));
-    return PGB_E_INVALID;
-  }
-  if (PGB_HEADERS_HASH == 0ull || rec.headers_hash != (uint64_t)PGB_HEADERS_HASH) {
-    snprintf(g_err, sizeof g_err, "the code object was compiled from other kernel headers (hash %016llx) than this library "
-             "(%016llx)", (unsigned long long)rec.headers_hash, (unsigned long long)PGB_HEADERS_HASH);
-    return PGB_E_INVALID;
-  }
-  if (rec.n_params != n_params) {
-    snprintf(g_err, sizeof g_err, "the code object was compiled for %d params, the call gives n_params = %d",
-             (int)rec.n_params, n_params);
-    return PGB_E_INVALID;
-  }
-  if (rec.n_outputs != K) {
-    snprintf(g_err, sizeof g_err, "the code object was compiled for %d outputs, %s = %d", (int)rec.n_outputs, k_side, K);
-    return PGB_E_INVALID;
-  }
-  const char* kernel = want_mark == PGB_COMPILED_MARK_SAMPLER ? PGB_PPC_COMPILED_KERNEL : PGB_POINTWISE_KERNEL;
-  if (hipModuleGetFunction(fn, *mod, kernel) != hipSuccess) {
-    (void)hipGetLastError();
-    snprintf(g_err, sizeof g_err, "the code object has no kernel %s", kernel);
-    return PGB_E_INVALID;
-  }
-  return PGB_OK;
-}
-
 extern "C" int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t* forest_tree_idx, int32_t n_forests,
                                     int32_t m, const double* X_dev, int64_t n_rows, int32_t p, int64_t ldx,
                                     const pgb_pointwise_lik* lik, double* loglik_dev_out, double* row_stats_dev_out,
@@ -110,29 +48,26 @@ extern "C" int pgb_pointwise_loglik(const pgb_tree_arrays* trees, const int32_t*
   if (lik->n_params > 0 && !lik->params_host) return fail(PGB_E_INVALID, "params_host is null");
   std::vector<double> hp((size_t)n_forests * PGB_PW_PSTRIDE, 0.0);
   const pgb_lltabs htb = pgb_lltabs_default();
-  for (int d = 0; d < n_forests; ++d) {
-    const double* src = lik->params_host + (size_t)d * lik->n_params;
-    double* dst = hp.data() + (size_t)d * PGB_PW_PSTRIDE;
-    if (compiled) {
-      for (int i = 0; i < lik->n_params; ++i) {
-        if (!(src[i] - src[i] == 0.0)) return fail(PGB_E_INVALID, "the compiled likelihood's params must be finite");
-        dst[i] = src[i];
-      }
-    } else if (pgb_logpdf_prepare(lik->family, src, dst, &htb) != 0) {
+  int bad_d = 0, bad_i = 0;
+  if (compiled && !compiled_params_table(lik->params_host, n_forests, lik->n_params, hp.data(), &bad_d, &bad_i))
+    return fail(PGB_E_INVALID, "the compiled likelihood's params must be finite");
+  for (int d = 0; d < n_forests && !compiled; ++d)
+    if (pgb_logpdf_prepare(lik->family, lik->params_host + (size_t)d * lik->n_params,
+                           hp.data() + (size_t)d * PGB_PW_PSTRIDE, &htb) != 0) {
       snprintf(g_err, sizeof g_err, "the params of draw %d are outside family %d's domain (positive and finite; 0 < q < 1)",
                d, (int)lik->family);
       return PGB_E_INVALID;
     }
-  }
   // ---- the history
   int rc = pred_validate(trees, forest_tree_idx, n_forests, m, p);
   if (rc != PGB_OK) return rc;
   hipStream_t sm = (hipStream_t)stream;
   PwScratch sc;
   hipFunction_t fn = nullptr;
+  pgb_compiled_layout rec;
   if (compiled) {
     rc = compiled_load_code(lik->code_object, lik->code_bytes, lik->n_params, K, "the trees have n_outputs",
-                            PGB_COMPILED_MARK_POINTWISE, "pgb_pointwise_loglik", &sc.mod, &fn);
+                            PGB_COMPILED_MARK_POINTWISE, "pgb_pointwise_loglik", &sc.mod, &fn, &rec);
     if (rc != PGB_OK) return rc;
   }
   // ---- the rows' columns: finite y / aux, a bounded offset (the tables are addressed by the predictor's bits)

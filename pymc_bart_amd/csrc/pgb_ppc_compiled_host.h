@@ -1,7 +1,7 @@
 // pgb_ppc_compiled_host.h -- part of pgbart_hip.hip (not a standalone header): host side of pgb_ppc_draw_compiled
 // (include/pgbart_ppc.h), the replicating call with a compiled likelihood's sampler body.  It shares the argument rules,
 // the grid and the launch sequence of pgb_ppc_draw (k_ppc.h: ppc_check_shape, ppc_check_ranges, ppc_run) and the
-// code-object checks of pgb_pointwise_loglik (pgb_pointwise_host.h: compiled_load_code, here with mark 2); the kernel
+// loader of every compiled code object (pgb_compiled_host.h: compiled_load_code, here with mark 2); the kernel
 // is the code object's k_ppc_compiled (k_ppc_compiled.hip).  Everything is checked before the launch.
 
 extern "C" int pgb_ppc_draw_compiled(const double* mu_dev, int32_t D, int32_t K, int64_t n_rows, int64_t ld, int64_t row0,
@@ -21,19 +21,16 @@ extern "C" int pgb_ppc_draw_compiled(const double* mu_dev, int32_t D, int32_t K,
   if (rc != PGB_OK) return rc;
   PpcScratch sc;
   hipFunction_t fn = nullptr;
+  pgb_compiled_layout rec;
   rc = compiled_load_code(code->code_object, code->code_bytes, code->n_params, K, "the call has K", PGB_COMPILED_MARK_SAMPLER,
-                          "pgb_ppc_draw_compiled", &sc.mod, &fn);
+                          "pgb_ppc_draw_compiled", &sc.mod, &fn, &rec);
   if (rc != PGB_OK) return rc;
   std::vector<double> hp((size_t)D * PGB_COMPILED_MAX_PARAMS, 0.0);
-  for (int d = 0; d < D; ++d)
-    for (int i = 0; i < code->n_params; ++i) {
-      const double v = code->params_host[(size_t)d * code->n_params + i];
-      if (!(v - v == 0.0)) {
-        snprintf(g_err, sizeof g_err, "the sampler body's params must be finite: param %d of draw %d is not", i, d);
-        return PGB_E_INVALID;
-      }
-      hp[(size_t)d * PGB_COMPILED_MAX_PARAMS + i] = v;
-    }
+  int bad_d = 0, bad_i = 0;
+  if (!compiled_params_table(code->params_host, D, code->n_params, hp.data(), &bad_d, &bad_i)) {
+    snprintf(g_err, sizeof g_err, "the sampler body's params must be finite: param %d of draw %d is not", bad_i, bad_d);
+    return PGB_E_INVALID;
+  }
   hipStream_t sm = (hipStream_t)stream;
   return ppc_run(sc, hp, mu_dev, D, K, n_rows, ld, row0, code->offset_dev, code->aux_dev, PGB_FAMILY_COMPILED, seed, out_dev,
                  ld_out, y_dev, pit_counts_dev, flags_host, sm, PGB_PPC_COMPILED_KERNEL, [&](const PpcArgs& A) {

@@ -84,6 +84,24 @@ def param_matrix(likelihood, points, D: int) -> np.ndarray:
     return np.ascontiguousarray(out[:, :n_par])
 
 
+def check_aux(likelihood, n: int):
+    """The aux column of a compiled likelihood against the ``n`` rows of ``X`` (``None`` without one)."""
+    aux = getattr(likelihood, "aux", None)
+    if aux is None:
+        return None
+    if aux.size != n:
+        raise ValueError(f"the compiled likelihood's aux must hold one value per row ({n}), got {aux.size}")
+    return np.ascontiguousarray(aux, np.float64)
+
+
+def take_code(lik, build):
+    """Hand a build's code object to the call's ``lik`` record (``code_object``, ``code_bytes``) -> the ctypes buffer
+    that holds the bytes: the caller keeps it for as long as ``lik`` is used."""
+    code = C.create_string_buffer(build.code, len(build.code))
+    lik.code_object, lik.code_bytes = C.cast(code, C.c_void_p), len(build.code)
+    return code
+
+
 class ScoringJob(Job):
     """One scoring call: the job base plus the family, ``y``, the compiled body's ``aux`` and the params per draw."""
 
@@ -96,11 +114,7 @@ class ScoringJob(Job):
         self.take_X(X)
         self.y = check_y(y, self.n)
         self.take_offset(offset)
-        self.aux = None
-        if self.family == "compiled" and likelihood.aux is not None:
-            if likelihood.aux.size != self.n:
-                raise ValueError(f"the compiled likelihood's aux must hold one value per row ({self.n}), got {likelihood.aux.size}")
-            self.aux = np.ascontiguousarray(likelihood.aux, np.float64)
+        self.aux = check_aux(likelihood, self.n) if self.family == "compiled" else None
         self.take_draws(draws, "no draws to score")
         self.params = param_matrix(likelihood, points, self.D)
         self.take_history()
@@ -117,11 +131,7 @@ class ScoringJob(Job):
         call = lib.pointwise_entry_point()
         n, D, K, p = self.n, self.D, self.K, self.p
         lik = fill_lik(_abi.PointwiseLik(), self)
-        code = None
-        if self.family == "compiled":
-            build = self.likelihood.compiled(pointwise=True)
-            code = C.create_string_buffer(build.code, len(build.code))
-            lik.code_object, lik.code_bytes = C.cast(code, C.c_void_p), len(build.code)
+        code = take_code(lik, self.likelihood.compiled(pointwise=True)) if self.family == "compiled" else None
         per_row = 8 * (p + 2 + K + (D if matrix else 0) + (4 * (-(-D // CHUNK)) + 3 if summary else 0)
                        + (int(scratch) if on_block is not None else 0))
         out = np.empty((D, n)) if matrix and on_block is None else None

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _abi
 from ._stored import Job, check_seed, check_y, drop_k_axis, fill_lik
-from .pointwise import FAMILY_OUTPUTS, FAMILY_PARAMS, check_outputs, param_matrix
+from .pointwise import FAMILY_OUTPUTS, FAMILY_PARAMS, check_aux, check_outputs, param_matrix, take_code
 from .summary import DEFAULT_HDI_PROB, DEFAULT_QUANTILES, result, spec, summary_block
 
 
@@ -54,16 +54,6 @@ def check_domain(family: str, params: np.ndarray) -> None:
                          f"0 < q < 1): {params[d].tolist()}")
 
 
-def check_aux(likelihood, n: int):
-    """The aux column of a compiled likelihood against the ``n`` rows of ``X`` (``None`` without one)."""
-    aux = getattr(likelihood, "aux", None)
-    if aux is None:
-        return None
-    if aux.size != n:
-        raise ValueError(f"the compiled likelihood's aux must hold one value per row ({n}), got {aux.size}")
-    return np.ascontiguousarray(aux, np.float64)
-
-
 class Replicator:
     """The replicating call of one job -- ``pgb_ppc_draw`` of a built-in family or ``pgb_ppc_draw_compiled`` of a
     compiled likelihood's sampler body -- for a block of rows, and the flag counts summed over the blocks.  ``job``
@@ -74,9 +64,8 @@ class Replicator:
         self.compiled = job.family == "compiled"
         if self.compiled:
             build = job.likelihood.compiled_sampler()
-            self._code = C.create_string_buffer(build.code, len(build.code))
             self.lik = lik = _abi.PpcCode()
-            lik.code_object, lik.code_bytes = C.cast(self._code, C.c_void_p), len(build.code)
+            self._code = take_code(lik, build)
             lik.n_params = job.n_par
             lik.params_host = job.params.ctypes.data if job.n_par else None
             self.call, self.name = lib.ppc_compiled_entry_point(), "pgb_ppc_draw_compiled"

@@ -373,6 +373,28 @@ class PGBLibrary:
         lib.pgb_row_reduce_workspace_bytes.restype = C.c_int64
         return lib.pgb_row_reduce, lib.pgb_row_reduce_finish, lib.pgb_row_reduce_workspace_bytes
 
+    def proximity_entry_points(self):
+        """``pgb_predict_leaf_codes``, ``pgb_prox_count``, ``pgb_prox_topk`` and ``pgb_prox_topk_workspace_bytes``
+        (include/pgbart_proximity.h): HIP library only, hence not in SYMBOLS.  A library without the symbols (the CPU
+        oracle) raises ``NotImplementedError`` naming the first."""
+        lib = self.lib
+        try:
+            codes = lib.pgb_predict_leaf_codes
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_predict_leaf_codes (HIP library only)") from None
+        codes.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                          C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        codes.restype = C.c_int
+        lib.pgb_prox_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        lib.pgb_prox_count.restype = C.c_int
+        lib.pgb_prox_topk.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_int32, C.c_void_p]
+        lib.pgb_prox_topk.restype = C.c_int
+        lib.pgb_prox_topk_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        lib.pgb_prox_topk_workspace_bytes.restype = C.c_int64
+        return codes, lib.pgb_prox_count, lib.pgb_prox_topk, lib.pgb_prox_topk_workspace_bytes
+
     def chain_diag_entry_point(self):
         """``pgb_chain_diag`` (include/pgbart_diag.h): HIP library only, hence not in SYMBOLS.  A library without the
         symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""

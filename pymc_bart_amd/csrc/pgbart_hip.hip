@@ -52,6 +52,7 @@
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
 #include "pgbart_rowreduce.h"
+#include "pgbart_proximity.h"
 #include "pgbart_diag.h"
 #include "pgbart_ppc.h"
 #include "pgbart_shap.h"
@@ -85,3 +86,4 @@
 #include "k_shap.h"
 #include "k_shap_interaction.h"
 #include "k_rowreduce.h"
+#include "k_proximity.h"

@@ -101,10 +101,10 @@ def table(so_path: str = SO) -> list[dict]:
             continue
         vg, ag = int(k[".vgpr_count"]), int(k.get(".agpr_count", 0))
         lds = int(k[".group_segment_fixed_size"])
-        # k_predict, k_pointwise<...>, k_ice<...>, k_pdp_walk<...>, k_shap<...>, k_shap_interaction<...>, k_psis,
-        # k_psis_expect<...>: one wave per workgroup (+ dynamic LDS)
-        threads = 64 if name.startswith(("k_predict", "k_pointwise<", "k_ice<", "k_pdp_walk<", "k_shap<", "k_shap_interaction<",
-                                         "k_psis_expect<")) \
+        # k_predict, k_leaf_codes<...>, k_pointwise<...>, k_ice<...>, k_pdp_walk<...>, k_shap<...>, k_shap_interaction<...>,
+        # k_psis, k_psis_expect<...>: one wave per workgroup (+ dynamic LDS)
+        threads = 64 if name.startswith(("k_predict", "k_leaf_codes<", "k_pointwise<", "k_ice<", "k_pdp_walk<", "k_shap<",
+                                         "k_shap_interaction<", "k_psis_expect<")) \
             or name == "k_psis" else 256
         occ = workgroups_per_cu(vg, ag, lds, threads)
         rows.append({"kernel": name, "vgpr": vg, "agpr": ag, "sgpr": int(k[".sgpr_count"]), "lds_bytes": lds,

@@ -21,6 +21,7 @@ from .loo import loo, loo_pit, loo_predictive, psis_expectation_matrix, psis_loo
 from .summary import posterior_summary, summarize_matrix
 from .diagnostics import convergence, diagnose_matrix, relative_efficiency
 from .predictive import posterior_predictive, predictive_pit, predictive_summary
+from .scores import predictive_scores, score_matrix
 from .average import average_contrast, average_prediction, bayes_r2
 from .proximity import leaf_ids, nearest_rows, proximity
 
@@ -46,6 +47,6 @@ __all__ = [
     "PGBART", "BARTOp", "CallbackLikelihood", "CompiledLikelihood", "CompileError", "compile_loglik", "NormalLikelihood", "BernoulliLikelihood", "CategoricalLikelihood", "NormalMeanScaleLikelihood", "PoissonLikelihood", "NegativeBinomialLikelihood", "AsymmetricLaplaceLikelihood", "StudentTLikelihood", "GammaLikelihood",
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
     "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix", "convergence", "diagnose_matrix", "relative_efficiency",
-    "posterior_predictive", "predictive_summary", "predictive_pit", "shap_values", "shap_summary", "shap_interaction_values", "shap_interaction_summary",
+    "posterior_predictive", "predictive_summary", "predictive_pit", "predictive_scores", "score_matrix", "shap_values", "shap_summary", "shap_interaction_values", "shap_interaction_summary",
     "average_prediction", "average_contrast", "bayes_r2", "leaf_ids", "proximity", "nearest_rows", "_abi",
 ]

@@ -358,6 +358,17 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def score_entry_point(self):
+        """``pgb_row_score`` (include/pgbart_score.h): HIP library only, hence not in SYMBOLS.  A library without the
+        symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_row_score
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_row_score (HIP library only)") from None
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     def rowreduce_entry_points(self):
         """``pgb_row_reduce``, ``pgb_row_reduce_finish`` and ``pgb_row_reduce_workspace_bytes``
         (include/pgbart_rowreduce.h): HIP library only, hence not in SYMBOLS."""

@@ -14,7 +14,8 @@
 //   3. values: the keys become t = f(a + off) in place (pgb_rowsum_value);
 //   4. statistics: one wave per column.  Lane l forms partial l of each lane sum and of the HDI scan, the partials go
 //      through LDS and are combined in lane order by the contract's own functions; lane j gathers quantile j.
-// No atomics, no floating-point reduction outside the contract's order.
+// No atomics, no floating-point reduction outside the contract's order.  Stages 1 and 2, the launch shape and the LDS
+// opt-in are functions of their own: k_rowscore (k_rowscore.h) starts from the same sorted tile.
 #define ROWSUM_BT 256
 #define ROWSUM_WAVES (ROWSUM_BT / 64)
 #define ROWSUM_MAX_KEYS 16384  /* keys of one workgroup: PGB_ROWSUM_MAX_DRAWS x 1 column = 2048 x 8 columns */
@@ -25,18 +26,13 @@ struct rowsum_q {
   double q[PGB_ROWSUM_MAX_Q];
 };
 
-__global__ __launch_bounds__(ROWSUM_BT) void k_rowsum(const double* __restrict__ a, int D, int lg, int lgC, long long n_cols,
-                                                      long long ld, const double* __restrict__ off, int transform, rowsum_q qs,
-                                                      int n_q, int hdi_k, double* __restrict__ out) {
-  __shared__ double s_part[ROWSUM_WAVES][PGB_ROWSUM_LANES];
-  __shared__ int32_t s_idx[ROWSUM_WAVES][PGB_ROWSUM_LANES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// Stages 1 and 2, shared with k_rowscore (k_rowscore.h): the keys of the workgroup's C x D tile of a [D][ld], columns
+// c0 .. c0 + C (columns beyond n_cols repeat the last one), padded to [C][Dp]; ends with a barrier
+__device__ __forceinline__ void rowsum_load_tile(unsigned long long* keys, const double* __restrict__ a, int D, int lg, int lgC,
+                                                 long long c0, long long n_cols, long long ld) {
+  const int tid = threadIdx.x;
   const int Dp = 1 << lg, C = 1 << lgC;
   const int total = C << lg;
-  const long long c0 = (long long)blockIdx.x << lgC;
-  unsigned long long* keys = rowsum_keys;
-
-  // ---- 1. the tile's keys (columns beyond n_cols repeat the last one), the padding
   const int n_el = D << lgC;
 #pragma unroll 4
   for (int e = tid; e < n_el; e += ROWSUM_BT) {
@@ -49,9 +45,13 @@ __global__ __launch_bounds__(ROWSUM_BT) void k_rowsum(const double* __restrict__
     for (int i = tid; i < total; i += ROWSUM_BT)
       if ((i & (Dp - 1)) >= D) keys[i] = PGB_ROWSUM_PAD_KEY;
   __syncthreads();
+}
 
-  // ---- 2. every column ascending
-  const int half = total >> 1;
+// ... and every column of the tile ascending; ends with a barrier
+__device__ __forceinline__ void rowsum_sort_tile(unsigned long long* keys, int lg, int lgC) {
+  const int tid = threadIdx.x;
+  const int Dp = 1 << lg;
+  const int half = (1 << (lg + lgC)) >> 1;
   for (int k = 2; k <= Dp; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int p = tid; p < half; p += ROWSUM_BT) {
@@ -66,6 +66,21 @@ __global__ __launch_bounds__(ROWSUM_BT) void k_rowsum(const double* __restrict__
       }
       __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(ROWSUM_BT) void k_rowsum(const double* __restrict__ a, int D, int lg, int lgC, long long n_cols,
+                                                      long long ld, const double* __restrict__ off, int transform, rowsum_q qs,
+                                                      int n_q, int hdi_k, double* __restrict__ out) {
+  __shared__ double s_part[ROWSUM_WAVES][PGB_ROWSUM_LANES];
+  __shared__ int32_t s_idx[ROWSUM_WAVES][PGB_ROWSUM_LANES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Dp = 1 << lg, C = 1 << lgC;
+  const int total = C << lg;
+  const long long c0 = (long long)blockIdx.x << lgC;
+  unsigned long long* keys = rowsum_keys;
+
+  rowsum_load_tile(keys, a, D, lg, lgC, c0, n_cols, ld);  // ---- 1. the tile's keys, the padding
+  rowsum_sort_tile(keys, lg, lgC);                        // ---- 2. every column ascending
 
   // ---- 3. t = f(a + off), in place
   pgb_lltabs tb;
@@ -122,6 +137,41 @@ __global__ __launch_bounds__(ROWSUM_BT) void k_rowsum(const double* __restrict__
   }
 }
 
+// The launch shape of both kernels: Dp = 1 << lg, C = 1 << lgC columns per workgroup, gx workgroups, lds bytes of keys
+struct rowsum_tiling {
+  int lg, lgC;
+  long long gx;
+  size_t lds;
+};
+
+static int rowsum_tile(int32_t D, int64_t n_cols, rowsum_tiling* g) {
+  g->lg = 1;
+  while ((1 << g->lg) < D) ++g->lg;
+  g->lgC = 3;
+  while (g->lgC > 0 && ((1 << g->lg) << g->lgC) > ROWSUM_MAX_KEYS) --g->lgC;
+  g->gx = (n_cols + (1ll << g->lgC) - 1) >> g->lgC;
+  if (g->gx > 0x7FFFFFFFll) return fail(PGB_E_UNSUPPORTED, "n_cols too large for one call");
+  g->lds = ((size_t)1 << (g->lg + g->lgC)) * sizeof(unsigned long long);
+  return PGB_OK;
+}
+
+// more than 64 KiB of dynamic LDS is an opt-in, per kernel and per device (opted: the devices that have it, the caller's)
+static int rowsum_lds_opt_in(const void* kernel, std::vector<int>* opted, const char* what) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  bool have = false;
+  for (int d : *opted) have = have || d == dev;
+  if (!have) {
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ROWSUM_MAX_KEYS * sizeof(unsigned long long)));
+    if (e != hipSuccess) return fail_hip(e, what);
+    opted->push_back(dev);
+  }
+  return PGB_OK;
+}
+
 extern "C" int pgb_row_summary(const double* a_dev, int32_t D, int64_t n_cols, int64_t ld, const double* offset_dev,
                                int32_t transform, const double* q_host, int32_t n_q, int32_t hdi_k, double* out_dev,
                                void* stream) {
@@ -152,34 +202,16 @@ extern "C" int pgb_row_summary(const double* a_dev, int32_t D, int64_t n_cols, i
     snprintf(g_err, sizeof g_err, "unknown transform %d", (int)transform);
     return PGB_E_INVALID;
   }
-  int lg = 1;
-  while ((1 << lg) < D) ++lg;
-  int lgC = 3;
-  while (lgC > 0 && ((1 << lg) << lgC) > ROWSUM_MAX_KEYS) --lgC;
-  const long long gx = (n_cols + (1ll << lgC) - 1) >> lgC;
-  if (gx > 0x7FFFFFFFll) return fail(PGB_E_UNSUPPORTED, "n_cols too large for one call");
-  const size_t lds = ((size_t)1 << (lg + lgC)) * sizeof(unsigned long long);
-  // more than 64 KiB of dynamic LDS is an opt-in, per device
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
-  static std::mutex mu;
+  rowsum_tiling g;
+  int rc = rowsum_tile(D, n_cols, &g);
+  if (rc != PGB_OK) return rc;
   static std::vector<int> opted;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    bool have = false;
-    for (int d : opted) have = have || d == dev;
-    if (!have) {
-      e = hipFuncSetAttribute((const void*)k_rowsum, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(ROWSUM_MAX_KEYS * sizeof(unsigned long long)));
-      if (e != hipSuccess) return fail_hip(e, "k_rowsum: dynamic LDS opt-in");
-      opted.push_back(dev);
-    }
-  }
+  rc = rowsum_lds_opt_in((const void*)k_rowsum, &opted, "k_rowsum: dynamic LDS opt-in");
+  if (rc != PGB_OK) return rc;
   hipStream_t sm = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_rowsum, dim3((unsigned)gx), dim3(ROWSUM_BT), lds, sm, a_dev, (int)D, lg, lgC, (long long)n_cols,
+  hipLaunchKernelGGL(k_rowsum, dim3((unsigned)g.gx), dim3(ROWSUM_BT), g.lds, sm, a_dev, (int)D, g.lg, g.lgC, (long long)n_cols,
                      (long long)ld, offset_dev, (int)transform, qs, (int)n_q, (int)hdi_k, out_dev);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "k_rowsum launch");
   e = hipStreamSynchronize(sm);
   if (e != hipSuccess) return fail_hip(e, "k_rowsum");

@@ -51,6 +51,7 @@
 #include "pgbart_psis.h"
 #include "pgbart_ice.h"
 #include "pgbart_rowsummary.h"
+#include "pgbart_score.h"
 #include "pgbart_rowreduce.h"
 #include "pgbart_proximity.h"
 #include "pgbart_diag.h"
@@ -79,6 +80,7 @@
 #include "k_psis.h"
 #include "k_ice.h"
 #include "k_rowsummary.h"
+#include "k_rowscore.h"
 #include "k_diag.h"
 #include "k_ppc.h"
 #include "pgb_ppc_compiled_host.h"

@@ -350,6 +350,19 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def predict_permuted_entry_point(self):
+        """``pgb_predict_permuted`` (include/pgbart_permimp.h): HIP library only, hence not in SYMBOLS.  A library
+        without the symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_predict_permuted
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_predict_permuted (HIP library only)") from None
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
+                      C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     def rowsummary_entry_point(self):
         """``pgb_row_summary`` (include/pgbart_rowsummary.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_row_summary

@@ -57,6 +57,7 @@
 #include "pgbart_diag.h"
 #include "pgbart_ppc.h"
 #include "pgbart_shap.h"
+#include "pgbart_permimp.h"
 
 #include "pgb_dims.h"
 
@@ -89,3 +90,4 @@
 #include "k_shap_interaction.h"
 #include "k_rowreduce.h"
 #include "k_proximity.h"
+#include "k_permimp.h"

@@ -42,8 +42,18 @@
  *                                   limits by tests/test_predict_edges_gpu.py
  *   SubsetSplit columns  integer category codes 0 .. 51 or NaN (the split value is a 52-bit mask in a double);
  *                        pgb_set_data checks every value and returns PGB_E_INVALID naming the column
+ *   covariates           under constant leaves any double or NaN (= missing), +-inf, subnormals and signed zeros
+ *                        included: a ContinuousSplit column enters only through the ORDER of its values, a OneHotSplit
+ *                        column only through their EQUALITY (tests/test_extremes.py, tests/test_extremes_gpu.py: chains
+ *                        on columns recoded onto neighbouring doubles, beyond the float32 range, onto -inf .. +inf)
  *   response linear/mix  any split rule (a leaf regresses on the column its parent split on, upstream's
- *                        fast_linear_fit; on a SubsetSplit column that is the category code)
+ *                        fast_linear_fit; on a SubsetSplit column that is the category code).  Every column needs
+ *                        max|x| < 2^1022 (PGB_LIN_MAX_EXPONENT: the row pass works with x 2^-ex): pgb_set_data returns
+ *                        PGB_E_INVALID naming the column otherwise.  A column with max|x| below about 2^-1020 is
+ *                        accepted, and its leaves are constant ones (slope 0).  Held by the same two files
+ *   range_exp            -480 .. 480 (PGB_MIN_RANGE_EXP .. PGB_MAX_RANGE_EXP, derived in pgbart_spec.h: every fixed-point
+ *                        scale is a normal double and a sum of n squared residuals stays finite); pgb_create returns
+ *                        PGB_E_INVALID otherwise.  Held at both ends by the same two files
  *   tree updates         < 2^32 per chain: the Philox counter takes the low 32 bits of the tree-update counter
  *                        (pgb_get_state's iter), so the random numbers of update i + 2^32 repeat those of update i
  *                        (about 4 days of cfg2-sized asteps at 12 k tree updates/s); nothing is refused

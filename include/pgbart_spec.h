@@ -181,6 +181,11 @@ PGB_HD double pgb_u2d(uint64_t u) {
   return x;
 }
 
+/* 2^e built from its bits.  DOMAIN: -1022 <= e <= 1023, the normal doubles.  Nothing is checked here (the row pass
+ * calls it per work item), and just outside the result is not even close: e = -1023 gives 0.0, -1024 gives -inf,
+ * -1025 gives -2^1023, 1024 gives +inf, 1025 gives -0.0.  Every caller with a data-dependent exponent is bounded where
+ * the data come in: the column exponents by PGB_LIN_MAX_EXPONENT and pgb_col_exponent's clamp (pgb_set_data), the
+ * fixed-point scales by PGB_MIN_RANGE_EXP / PGB_MAX_RANGE_EXP (pgb_create). */
 PGB_HD double pgb_pow2(int e) { return pgb_u2d((uint64_t)(e + 1023) << 52); }
 
 /* ------------------------------------------------------------------ split rules */
@@ -725,6 +730,18 @@ PGB_HD int64_t pgb_quant(double x, double scale, unsigned* sat) {
  *   S2   = frac - 2*range_exp              for squared residual terms
  *   SL   = frac - 11                       for per-row log-likelihood terms (|x| < 2048)
  * so that n saturated terms still fit an int64.                                  */
+/* The range_exp a sampler may be created with (pgb_create refuses anything else with PGB_E_INVALID).  Every scale
+ * below, its inverse and the linear response's R = 2^(range_exp - 1) / 2^(1 - range_exp) go through pgb_pow2 and must
+ * be NORMAL doubles for every n < 2^31, i.e. for frac = 30 .. 50:
+ *     |frac - 2 range_exp| <= 1022   (S2 and -S2; S1 and R are half as far out)
+ *         frac = 50, range_exp < 0:  range_exp >= -486;      frac = 30, range_exp > 0:  range_exp <= 526
+ * and a sum of n squared residuals, each below 2^(2 range_exp), must stay a finite double (the SSE of a leaf,
+ * pgb_leaf_sse, before sigma^-2 scales it back):
+ *     2 range_exp + 31 < 1024        range_exp <= 496
+ * which leaves [-486, 496]; the ends are taken round, inside it.  (The CPU oracle at n = 1025 runs a Normal chain as
+ * the exactly scaled chain for range_exp = -486 .. 512 and not beyond; tests/test_extremes.py holds both ends.) */
+#define PGB_MIN_RANGE_EXP (-480)
+#define PGB_MAX_RANGE_EXP 480
 typedef struct {
   double c1, c2, cl;             /* 2^S1, 2^S2, 2^SL   */
   double inv_c1, inv_c2, inv_cl; /* 2^-S1, 2^-S2, 2^-SL */
@@ -862,7 +879,15 @@ PGB_HD double pgb_lin_sse(double sse_const, pgb_linfit f, int64_t q_ur, int64_t 
   double sse = (sse_const - (2.0 * f.slope_u) * cru) + (f.slope_u * f.slope_u) * f.var_u;
   return sse;
 }
-/* exponent bound of a column: smallest ex >= 0... any integer ex with max|x| <= 2^ex */
+/* exponent bound of a column: smallest ex >= 0... any integer ex with max|x| <= 2^ex.
+ * Both 2^ex and 2^-ex go through pgb_pow2, so a column is regressed on only while ex <= PGB_LIN_MAX_EXPONENT, i.e.
+ * max|x| < 2^1022 (ex = 1023 would make 2^-ex = 0.0: every slope lost without a word; an infinite value makes
+ * ex = 1025): pgb_set_data refuses a linear / mix sampler anything larger, naming the column.  Constant leaves never
+ * come here and take any double.
+ * At the small end nothing is refused: ex is clamped at -1000, so u = x 2^1000 is exact and |u| <= 1 for any column,
+ * but a column with max|x| below about 2^-1020 has a spread of u under pgb_lin_fit's `var > 1e-12` test and its leaves
+ * are constant ones (slope 0). */
+#define PGB_LIN_MAX_EXPONENT 1022
 PGB_HD int pgb_col_exponent(double amax) {
   if (!(amax > 0.0)) return 0;
   int e = (int)((pgb_d2u(amax) >> 52) & 0x7FF) - 1023 + 1; /* amax < 2^e */

@@ -201,6 +201,12 @@ int pgb_create(const pgb_settings* s, void* stream, pgb_handle** out) {
   }
   if (s->batch_tune < 1 || s->batch_draw < 1) return fail(PGB_E_INVALID, "batch sizes must be >= 1");
   if (s->compat & ~PGB_COMPAT_ALL) return fail(PGB_E_INVALID, "unknown compat bits (pgbart_spec.h: PGB_COMPAT_*)");
+  if (s->range_exp < PGB_MIN_RANGE_EXP || s->range_exp > PGB_MAX_RANGE_EXP) { /* (the scales are built from its bits: pgb_pow2) */
+    static __thread char msg[160];
+    snprintf(msg, sizeof msg, "range_exp = %d is outside [%d, %d] (PGB_MIN_RANGE_EXP, PGB_MAX_RANGE_EXP: the fixed-point scales must be normal doubles)",
+             (int)s->range_exp, PGB_MIN_RANGE_EXP, PGB_MAX_RANGE_EXP);
+    return fail(PGB_E_INVALID, msg);
+  }
   if (s->response != PGB_RESPONSE_CONSTANT) {
     if (s->response != PGB_RESPONSE_LINEAR && s->response != PGB_RESPONSE_MIX)
       return fail(PGB_E_UNSUPPORTED, "unknown response");
@@ -300,6 +306,12 @@ int pgb_set_data(pgb_handle* h, const double* X, int64_t ldx, const int32_t* rul
       if (a > amax) amax = a; /* NaN compares false */
     }
     h->col_ex[j] = pgb_col_exponent(amax);
+    if (h->s.response != PGB_RESPONSE_CONSTANT && h->col_ex[j] > PGB_LIN_MAX_EXPONENT) { /* 2^-ex would not be a normal double */
+      static __thread char msg[200];
+      snprintf(msg, sizeof msg, "response linear / mix: column %d has max|x| = %g, a regressed column needs max|x| < 2^%d (PGB_LIN_MAX_EXPONENT)",
+               j, amax, PGB_LIN_MAX_EXPONENT);
+      return fail(PGB_E_INVALID, msg);
+    }
     if (rules[j] == PGB_RULE_SUBSET) /* category codes outside 0 .. 51 are refused, not clamped */
       for (int64_t i = 0; i < n; ++i) {
         double x = h->X[(size_t)j * n + i];

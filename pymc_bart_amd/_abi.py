@@ -20,6 +20,7 @@ MAX_DEPTH = 64
 MAX_PARTICLES = 128  # of the p128 build of the library; the default build takes 64 (PGBLibrary.max_particles)
 MAX_OUTPUTS = 16  # PGB_MAX_OUTPUTS (include/pgbart_spec.h)
 MAX_NODES = 255
+MIN_RANGE_EXP, MAX_RANGE_EXP = -480, 480  # PGB_MIN_RANGE_EXP, PGB_MAX_RANGE_EXP (include/pgbart_spec.h)
 PDP_LDS_MAXB = 256  # PGB_PDP_LDS_MAXB (include/pgbart_pdp.h)
 SHAP_FAST_U = 8  # PGB_SHAP_FAST_U (include/pgbart_shap.h)
 SHAPX_MAX_U = 32  # PGB_SHAPX_MAX_U (include/pgbart_shap_interaction.h)

@@ -121,15 +121,24 @@ class PyBartSettings:
         partial residuals far outside the data's own range."""
         Y = np.asarray(Y, np.float64)
         n, p = X.shape
+        rexp = range_exponent(Y) if y_obs is None else range_exponent(Y, y_obs)
+        if range_exp is not None:
+            rexp = int(range_exp)
+            if not _abi.MIN_RANGE_EXP <= rexp <= _abi.MAX_RANGE_EXP:
+                raise ValueError(f"range_exp = {rexp} is outside [{_abi.MIN_RANGE_EXP}, {_abi.MAX_RANGE_EXP}], the "
+                                 "fixed-point ranges the sampler can be built for (include/pgbart_spec.h)")
+        elif not _abi.MIN_RANGE_EXP <= rexp <= _abi.MAX_RANGE_EXP:
+            # (before anything native is created: pgb_create would refuse the settings without knowing why they are such)
+            amax = max(float(np.nanmax(np.abs(np.asarray(a, np.float64)))) for a in ((Y,) if y_obs is None else (Y, y_obs)))
+            raise ValueError(f"the response has max|y| = {amax:.6g}: its fixed-point range 2^{rexp} is outside "
+                             f"[2^{_abi.MIN_RANGE_EXP}, 2^{_abi.MAX_RANGE_EXP}], what the sampler can be built for -- "
+                             "rescale the response (and sigma with it)")
+        elif family != "normal":
+            rexp = max(rexp, 10)  # latent link scale: |sum_trees| < 1024 (separable data drifts far)
         mean = float(Y.mean())
         is_binary = bool(np.all((Y == 0) | (Y == 1)))
         # [U] leaf_sd = 3/sqrt(m) for 0/1 responses, std(Y)/sqrt(m) otherwise
         leaf_sd = 3.0 / math.sqrt(m) if is_binary else float(Y.std()) / math.sqrt(m)
-        rexp = range_exponent(Y) if y_obs is None else range_exponent(Y, y_obs)
-        if range_exp is not None:
-            rexp = int(range_exp)
-        elif family != "normal":
-            rexp = max(rexp, 10)  # latent link scale: |sum_trees| < 1024 (separable data drifts far)
         return cls(
             n=n, p=p, m=m, num_particles=num_particles, n_outputs=n_outputs, family=family,
             alpha=alpha, beta=beta, batch=tuple(batch), seed=int(seed), init_sum=mean,

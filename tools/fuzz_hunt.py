@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Parity hunt on a GPU box: random configurations (tests/_cases.random_case) through the HIP library and
 the CPU oracle, bit-for-bit digests compared.
-usage: python tools/fuzz_hunt.py FIRST_SEED COUNT [SECONDS] [large] [compat] [mk] [migrate] [--caps]
+usage: python tools/fuzz_hunt.py FIRST_SEED COUNT [SECONDS] [large] [compat] [mk] [migrate] [--caps] [--extremes]
 (--caps: the configurations of tests/_cases.random_cap_case instead -- trees driven into the limits of 255 nodes and
 depth 64; the share of oracle runs that a limit stops (cap_reach) is printed; large and compat do not apply;
 large: n = 50k .. 1M, few trees; compat: the upstream-semantics switches on, PGB_COMPAT_* = 1 + seed % 3;
 mk: only the configurations with K-vector leaves -- the seeds of the others are skipped;
 migrate: the GPU chain is moved to the oracle and back through the chain image -- pgb_checkpoint_save / _load,
-include/pgbart_image.h -- at random steps, and must still be the chain the oracle runs alone)"""
+include/pgbart_image.h -- at random steps, and must still be the chain the oracle runs alone;
+--extremes: every continuous column of the configuration is recoded onto a random ladder of tests/_extreme_cases.py --
+neighbouring doubles, beyond the float32 range, subnormals, -inf .. +inf -- by draws of their own, made after the
+configuration's; the HIP chain on the recoded data must be the oracle's there AND, but for the split values, the HIP
+chain on the data as drawn.  Constant leaves only: the seeds of linear / mix configurations are skipped.  Run it with
+PGB_X32_MIN_MB=0 as well: the order keys of such columns)"""
 import os
 import sys
 import time
@@ -21,12 +26,13 @@ from _oracle import oracle_backend  # noqa: E402
 from pymc_bart_amd.sampler import default_backend  # noqa: E402
 
 first, count = int(sys.argv[1]), int(sys.argv[2])
-budget = float(sys.argv[3]) if len(sys.argv) > 3 and sys.argv[3] != "--caps" else 1e9
+budget = float(sys.argv[3]) if len(sys.argv) > 3 and not sys.argv[3].startswith("--") else 1e9
 large = "large" in sys.argv[4:]
 compat_on = "compat" in sys.argv[4:]
 mk_only = "mk" in sys.argv[4:]
 migrate = "migrate" in sys.argv[4:]
 caps = "--caps" in sys.argv[3:]
+extremes = "--extremes" in sys.argv[3:]
 import numpy as np  # noqa: E402
 hip, orc = default_backend(0), oracle_backend()
 t0, bad, done, at_a_limit = time.time(), [], 0, 0
@@ -37,7 +43,15 @@ for seed in range(first, first + count):
     c = random_cap_case(seed) if caps else random_case(seed, large, compat=(1 + seed % 3) if compat_on else 0)
     if mk_only and int(c["K"]) < 2:
         continue
-    cuts = ()
+    if extremes and str(c.get("response", "constant")) != "constant":
+        continue
+    cuts, plain = (), None
+    if extremes:
+        from _extreme_cases import LADDERS, remap
+
+        r = np.random.default_rng([seed, 0xE])
+        plain = run_case(c, hip)
+        c = dict(c, X=remap(c["X"], [str(r.choice(LADDERS)) if rule == 0 else None for rule in c["rules"]])[0])
     if migrate:  # 1..4 cuts, the chain alternating between the backends (the first move is to the oracle)
         r = np.random.default_rng(seed)
         at = sorted(set(int(x) for x in r.integers(1, max(2, c["steps"]), size=int(r.integers(1, 5)))))
@@ -50,6 +64,13 @@ for seed in range(first, first + count):
     done += 1
     key = (c["family"], int(c["K"]), str(c.get("response", "constant")))
     fam[key] = fam.get(key, 0) + 1
+    if plain is not None:  # rank invariance on the device: everything but the split values is where it was
+        f0, f1 = plain["forest"], ores["forest"]
+        same = (np.array_equal(plain["sum_trees"], ores["sum_trees"]) and np.array_equal(plain["vi"], ores["vi"])
+                and plain["counters"] == ores["counters"] and np.array_equal(f0.var, f1.var)
+                and np.array_equal(f0.count, f1.count) and np.array_equal(f0.value, f1.value))
+        if not same:
+            g = None
     if g != o:
         bad.append(seed)
         print("MISMATCH", seed, c["family"], c["X"].shape, c["m"], c["P"], c["K"], c["rules"].tolist(), flush=True)

@@ -364,6 +364,19 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def predict_ale_entry_point(self):
+        """``pgb_predict_ale`` (include/pgbart_ale.h): HIP library only, hence not in SYMBOLS.  A library without the
+        symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_predict_ale
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_predict_ale (HIP library only)") from None
+        f.argtypes = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                      C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                      C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
     def rowsummary_entry_point(self):
         """``pgb_row_summary`` (include/pgbart_rowsummary.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_row_summary

@@ -58,6 +58,7 @@
 #include "pgbart_ppc.h"
 #include "pgbart_shap.h"
 #include "pgbart_permimp.h"
+#include "pgbart_ale.h"
 
 #include "pgb_dims.h"
 
@@ -91,3 +92,4 @@
 #include "k_rowreduce.h"
 #include "k_proximity.h"
 #include "k_permimp.h"
+#include "k_ale.h"

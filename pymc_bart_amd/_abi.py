@@ -377,6 +377,44 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def hstat_entry_points(self):
+        """``pgb_hstat_workspace_bytes``, ``pgb_hstat_background``, ``pgb_hstat_rows`` and ``pgb_hstat_finish``
+        (include/pgbart_hstat.h): HIP library only, hence not in SYMBOLS.  A library without a symbol (the CPU
+        oracle) raises ``NotImplementedError`` naming it."""
+        jobs = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]  # cols, q, pairs, n_pairs, picks, n_picks
+        history = [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32]
+        block = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32]  # X, nb, p, ldx, w, first_row, init
+        signatures = {
+            "pgb_hstat_workspace_bytes": history + [C.c_int32] + jobs + [C.POINTER(C.c_int64), C.c_void_p],
+            "pgb_hstat_background": history + block + jobs + [C.c_void_p, C.c_void_p],
+            "pgb_hstat_rows": history + block + jobs + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+            "pgb_hstat_finish": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p],
+        }
+        fns = []
+        for name, argtypes in signatures.items():
+            try:
+                f = getattr(self.lib, name)
+            except AttributeError:
+                raise NotImplementedError(f"{self.path} does not export {name} (HIP library only)") from None
+            f.argtypes = argtypes
+            f.restype = C.c_int
+            fns.append(f)
+        return tuple(fns)
+
+    def hstat_kernel_ms(self) -> tuple:
+        """``pgb_hstat_kernel_ms``: the last ``(k_hstat_bg, k_hstat_rows)`` times of this thread under
+        ``PGB_WALK_TIMING=1`` in milliseconds (-1.0: none yet)."""
+        try:
+            f = self.lib.pgb_hstat_kernel_ms
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_hstat_kernel_ms (HIP library only)") from None
+        f.argtypes = [C.POINTER(C.c_double)]
+        f.restype = C.c_int
+        ms = (C.c_double * 2)()
+        self.check(f(ms), "pgb_hstat_kernel_ms")
+        return float(ms[0]), float(ms[1])
+
     def rowsummary_entry_point(self):
         """``pgb_row_summary`` (include/pgbart_rowsummary.h): HIP library only, hence not in SYMBOLS."""
         f = self.lib.pgb_row_summary

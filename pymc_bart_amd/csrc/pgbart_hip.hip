@@ -59,6 +59,7 @@
 #include "pgbart_shap.h"
 #include "pgbart_permimp.h"
 #include "pgbart_ale.h"
+#include "pgbart_hstat.h"
 
 #include "pgb_dims.h"
 
@@ -93,3 +94,4 @@
 #include "k_proximity.h"
 #include "k_permimp.h"
 #include "k_ale.h"
+#include "k_hstat.h"

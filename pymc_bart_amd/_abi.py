@@ -377,6 +377,46 @@ class PGBLibrary:
         f.restype = C.c_int
         return f
 
+    def arms_entry_points(self):
+        """``pgb_predict_arms``, ``pgb_arm_decide``, ``pgb_arm_decide_finish`` and ``pgb_arm_decide_workspace_bytes``
+        (include/pgbart_arms.h): HIP library only, hence not in SYMBOLS.  A library without a symbol (the CPU oracle)
+        raises ``NotImplementedError`` naming it."""
+        signatures = {
+            "pgb_predict_arms": (C.c_int, [C.POINTER(TreeArraysC), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "pgb_arm_decide": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32,
+                                         C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+            "pgb_arm_decide_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int64), C.c_void_p]),
+            "pgb_arm_decide_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+        }
+        fns = []
+        for name, (restype, argtypes) in signatures.items():
+            try:
+                f = getattr(self.lib, name)
+            except AttributeError:
+                raise NotImplementedError(f"{self.path} does not export {name} (HIP library only)") from None
+            f.argtypes = argtypes
+            f.restype = restype
+            fns.append(f)
+        return tuple(fns)
+
+    def arms_kernel_ms(self) -> tuple:
+        """``pgb_arms_kernel_ms``: the last ``(k_arms, the decide kernels)`` times of this thread under
+        ``PGB_WALK_TIMING=1`` in milliseconds (-1.0: none yet)."""
+        try:
+            f = self.lib.pgb_arms_kernel_ms
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_arms_kernel_ms (HIP library only)") from None
+        f.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        f.restype = C.c_int
+        walk, decide = C.c_double(), C.c_double()
+        self.check(f(C.byref(walk), C.byref(decide)), "pgb_arms_kernel_ms")
+        return float(walk.value), float(decide.value)
+
     def hstat_entry_points(self):
         """``pgb_hstat_workspace_bytes``, ``pgb_hstat_background``, ``pgb_hstat_rows`` and ``pgb_hstat_finish``
         (include/pgbart_hstat.h): HIP library only, hence not in SYMBOLS.  A library without a symbol (the CPU

@@ -60,6 +60,7 @@
 #include "pgbart_permimp.h"
 #include "pgbart_ale.h"
 #include "pgbart_hstat.h"
+#include "pgbart_arms.h"
 
 #include "pgb_dims.h"
 
@@ -95,3 +96,4 @@
 #include "k_permimp.h"
 #include "k_ale.h"
 #include "k_hstat.h"
+#include "k_arms.h"

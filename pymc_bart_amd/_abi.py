@@ -417,6 +417,31 @@ class PGBLibrary:
         self.check(f(C.byref(walk), C.byref(decide)), "pgb_arms_kernel_ms")
         return float(walk.value), float(decide.value)
 
+    def surv_entry_points(self):
+        """``pgb_surv_curves`` (include/pgbart_surv.h): HIP library only, hence not in SYMBOLS.  A library without the
+        symbol (the CPU oracle) raises ``NotImplementedError`` naming it."""
+        try:
+            f = self.lib.pgb_surv_curves
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_surv_curves (HIP library only)") from None
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                      C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        return f
+
+    def surv_kernel_ms(self) -> float:
+        """``pgb_surv_kernel_ms``: the last ``k_surv`` time of this thread under ``PGB_WALK_TIMING=1`` in milliseconds
+        (-1.0: none yet)."""
+        try:
+            f = self.lib.pgb_surv_kernel_ms
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_surv_kernel_ms (HIP library only)") from None
+        f.argtypes = [C.POINTER(C.c_double)]
+        f.restype = C.c_int
+        ms = C.c_double()
+        self.check(f(C.byref(ms)), "pgb_surv_kernel_ms")
+        return float(ms.value)
+
     def hstat_entry_points(self):
         """``pgb_hstat_workspace_bytes``, ``pgb_hstat_background``, ``pgb_hstat_rows`` and ``pgb_hstat_finish``
         (include/pgbart_hstat.h): HIP library only, hence not in SYMBOLS.  A library without a symbol (the CPU

@@ -61,6 +61,7 @@
 #include "pgbart_ale.h"
 #include "pgbart_hstat.h"
 #include "pgbart_arms.h"
+#include "pgbart_surv.h"
 
 #include "pgb_dims.h"
 
@@ -97,3 +98,4 @@
 #include "k_ale.h"
 #include "k_hstat.h"
 #include "k_arms.h"
+#include "k_surv.h"

@@ -55,6 +55,20 @@ def check_arms(arms, s: int) -> np.ndarray:
     return np.ascontiguousarray(arms)
 
 
+def with_draw_stats(res: dict, per_draw: dict, hdi_prob: float) -> dict:
+    """``res`` with every per-draw array ``(D, ...)`` of ``per_draw`` and its ``_mean``, ``_sd`` and ``_hdi`` over the
+    draws."""
+    for key, a in per_draw.items():
+        flat = a.reshape(a.shape[0], -1)
+        lo_hi = np.empty((flat.shape[1], 2))
+        for j in range(flat.shape[1]):
+            lo_hi[j] = hdi(flat[:, j], hdi_prob)
+        with np.errstate(invalid="ignore"):
+            res.update({key: a, key + "_mean": a.mean(axis=0), key + "_sd": a.std(axis=0),
+                        key + "_hdi": lo_hi.reshape(a.shape[1:] + (2,))})
+    return res
+
+
 class ArmsJob(Job):
     """One call of this module.  The arguments are taken in this order: ``X``, the columns, the arms, the draws and --
     :func:`optimal_arm` only -- ``output``, the transform, the offset, the costs, the weights, the groups, the policy,
@@ -75,14 +89,13 @@ class ArmsJob(Job):
         self.take_draws(draws, none="a decision needs at least 1 draw")
         self.picks = np.arange(self.D, dtype=np.int32)
 
-    def take_decision(self, output, transform, offset, cost, maximize, weights, groups, policy, hdi_prob):
+    def take_output(self, output):
         if isinstance(output, (bool, np.bool_)) or not isinstance(output, (int, np.integer)) or not 0 <= int(output) < self.K:
             raise ValueError(f"output must be an integer in [0, {self.K}), got {output!r}")
         self.output = int(output)
-        transform = "identity" if transform is None else transform
-        if transform not in TRANSFORMS:
-            raise ValueError(f"unknown transform {transform!r}: use one of {', '.join(TRANSFORMS)}")
-        self.code = TRANSFORMS[transform]
+
+    def take_row_offset(self, offset):
+        """The offset of the one output a call reads: ``(n,)``."""
         self.off = None
         if offset is not None:
             off = np.asarray(offset, dtype=np.float64)
@@ -91,6 +104,26 @@ class ArmsJob(Job):
             if not np.all(np.isfinite(off)) or np.max(np.abs(off)) > MAX_OFFSET:
                 raise ValueError(f"offset must be finite and within +-{MAX_OFFSET:g}")
             self.off = np.ascontiguousarray(off)
+
+    def take_rows(self, weights, groups):
+        """The weights and the groups of the averages over the rows."""
+        self.weights = check_weights(weights, self.n)
+        self.labels, self.gid, self.n_rows = check_groups(groups, self.n, self.weights)
+        self.G = int(self.labels.size)
+
+    def take_hdi_prob(self, hdi_prob):
+        """The mass of the intervals over the draws of the per-draw results."""
+        if not 0.0 < float(hdi_prob) < 1.0:
+            raise ValueError(f"hdi_prob must lie in (0, 1), got {hdi_prob!r}")
+        self.hdi_prob = float(hdi_prob)
+
+    def take_decision(self, output, transform, offset, cost, maximize, weights, groups, policy, hdi_prob):
+        self.take_output(output)
+        transform = "identity" if transform is None else transform
+        if transform not in TRANSFORMS:
+            raise ValueError(f"unknown transform {transform!r}: use one of {', '.join(TRANSFORMS)}")
+        self.code = TRANSFORMS[transform]
+        self.take_row_offset(offset)
         self.cost = None
         if cost is not None:
             c = np.asarray(cost, dtype=np.float64)
@@ -100,9 +133,7 @@ class ArmsJob(Job):
                 raise ValueError("cost must be finite")
             self.cost = np.ascontiguousarray(c)
         self.sign = 1.0 if maximize else -1.0
-        self.weights = check_weights(weights, self.n)
-        self.labels, self.gid, self.n_rows = check_groups(groups, self.n, self.weights)
-        self.G = int(self.labels.size)
+        self.take_rows(weights, groups)
         self.policy = None
         if policy is not None:
             pol = np.asarray(policy)
@@ -112,9 +143,7 @@ class ArmsJob(Job):
             if pol.min() < 0 or pol.max() >= self.A:
                 raise ValueError(f"policy must index the {self.A} arms")
             self.policy = np.ascontiguousarray(pol, dtype=np.int32)
-        if not 0.0 < float(hdi_prob) < 1.0:
-            raise ValueError(f"hdi_prob must lie in (0, 1), got {hdi_prob!r}")
-        self.hdi_prob = float(hdi_prob)
+        self.take_hdi_prob(hdi_prob)
         self.ws_bytes = workspace_bytes(self.D, self.G, self.A)
         if self.ws_bytes > block_bytes(*PW_BLOCK):
             raise ValueError(f"the partial sums of {self.D} draws x {self.G} groups x {self.A} arms take {self.ws_bytes} bytes, "
@@ -132,9 +161,8 @@ class ArmsJob(Job):
         return self.predict_row_bytes() + 12 * self.D + 8 + 4 + 4 + 8 + self.A * (4 + 8 + 8) + 4
 
     # ------------------------------------------------------------------ the run
-    def hip(self):
-        """The backend and the entry points; the CPU oracle has none: ``NotImplementedError`` naming
-        ``pgb_predict_arms``."""
+    def pick_backend(self):
+        """The backend of the call: the one given, the sampler's, or the default one."""
         be = self.given_backend
         if be is None:
             if self.backend is not None:
@@ -143,15 +171,24 @@ class ArmsJob(Job):
                 from .sampler import default_backend
 
                 be = default_backend()
+        return be
+
+    def hip(self):
+        """The backend and the entry points; the CPU oracle has none: ``NotImplementedError`` naming
+        ``pgb_predict_arms``."""
+        be = self.pick_backend()
         return be, be.lib.arms_entry_points()
 
-    def arms_block(self, be, predict_arms, blk, lens):
-        """``pgb_predict_arms`` of one block -> the device matrix ``[A][D][K][nb]``."""
+    def arms_block(self, be, predict_arms, blk, lens, arms=None):
+        """``pgb_predict_arms`` of one block -> the device matrix ``[A][D][K][nb]``.  ``arms``: ``(A, s)`` float64 and
+        contiguous (default: the job's own)."""
         mem, nb = be.mem, blk.nb
-        od = mem.empty((self.A * self.D * self.K * nb,), np.float64)
+        arms = self.arms if arms is None else arms
+        A = int(arms.shape[0])
+        od = mem.empty((A * self.D * self.K * nb,), np.float64)
         carr = self.pool.as_c()
         rc = predict_arms(C.byref(carr), self.fidx.ctypes.data, self.D, self.m, mem.ptr(blk.xd), nb, self.p, self.p,
-                          self.cols.ctypes.data, self.s, self.arms.ctypes.data, self.A, self.picks.ctypes.data, self.D,
+                          self.cols.ctypes.data, self.s, arms.ctypes.data, A, self.picks.ctypes.data, self.D,
                           mem.ptr(blk.md), mem.ptr(od), lens.ctypes.data, mem.stream_ptr)
         be.lib.check(rc, "pgb_predict_arms")
         return od
@@ -211,15 +248,7 @@ class ArmsJob(Job):
                     "share_best": np.ascontiguousarray(np.moveaxis(out[4 + A:], 0, -1))}
         if self.policy is not None:
             per_draw["value_policy"] = out[2].copy()
-        for key, a in per_draw.items():
-            flat = a.reshape(D, -1)
-            lo_hi = np.empty((flat.shape[1], 2))
-            for j in range(flat.shape[1]):
-                lo_hi[j] = hdi(flat[:, j], self.hdi_prob)
-            with np.errstate(invalid="ignore"):
-                res.update({key: a, key + "_mean": a.mean(axis=0), key + "_sd": a.std(axis=0),
-                            key + "_hdi": lo_hi.reshape(a.shape[1:] + (2,))})
-        return res
+        return with_draw_stats(res, per_draw, self.hdi_prob)
 
 
 def arm_predictions(sampler, X, cols, arms, *, draws=None, backend=None) -> np.ndarray:

@@ -29,6 +29,7 @@ from .ale import accumulated_local_effects, ale_edges
 from .hstat import friedman_h
 from .decision import arm_predictions, optimal_arm
 from .survival import person_period, survival_curves, survival_matrix
+from .discrimination import discrimination, discrimination_matrix
 
 
 def _register_step_method():
@@ -53,5 +54,5 @@ __all__ = [
     "PyBartSettings", "PySampler", "TreeArrays", "PosteriorSampler", "compute_variable_importance", "get_variable_inclusion", "vi_to_kulprit",
     "partial_dependence", "individual_conditional_expectation", "pdp_sweep", "pointwise_log_likelihood", "log_predictive_density", "loo", "psis_loo_matrix", "loo_pit", "loo_predictive", "psis_expectation_matrix", "posterior_summary", "summarize_matrix", "convergence", "diagnose_matrix", "relative_efficiency",
     "posterior_predictive", "predictive_summary", "predictive_pit", "predictive_scores", "score_matrix", "shap_values", "shap_summary", "shap_interaction_values", "shap_interaction_summary",
-    "average_prediction", "average_contrast", "bayes_r2", "permutation_importance", "accumulated_local_effects", "ale_edges", "friedman_h", "arm_predictions", "optimal_arm", "person_period", "survival_curves", "survival_matrix", "leaf_ids", "proximity", "nearest_rows", "_abi",
+    "average_prediction", "average_contrast", "bayes_r2", "permutation_importance", "accumulated_local_effects", "ale_edges", "friedman_h", "arm_predictions", "optimal_arm", "person_period", "survival_curves", "survival_matrix", "discrimination", "discrimination_matrix", "leaf_ids", "proximity", "nearest_rows", "_abi",
 ]

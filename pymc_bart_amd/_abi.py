@@ -442,6 +442,41 @@ class PGBLibrary:
         self.check(f(C.byref(ms)), "pgb_surv_kernel_ms")
         return float(ms.value)
 
+    def rank_entry_points(self):
+        """``pgb_rank_keys``, ``pgb_rank_workspace_bytes`` and ``pgb_rank_metrics`` (include/pgbart_rank.h): HIP
+        library only, hence not in SYMBOLS.  A library without them (the CPU oracle) raises ``NotImplementedError``
+        naming ``pgb_rank_metrics``."""
+        signatures = {
+            "pgb_rank_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "pgb_rank_keys": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+            "pgb_rank_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+        }
+        fns = {}
+        for name, (restype, argtypes) in signatures.items():
+            try:
+                f = getattr(self.lib, name)
+            except AttributeError:
+                raise NotImplementedError(f"{self.path} does not export pgb_rank_metrics (HIP library only)") from None
+            f.argtypes = argtypes
+            f.restype = restype
+            fns[name] = f
+        return fns["pgb_rank_keys"], fns["pgb_rank_workspace_bytes"], fns["pgb_rank_metrics"]
+
+    def rank_kernel_ms(self) -> tuple:
+        """``pgb_rank_kernel_ms``: the last ``(k_rank_keys, segmented sort, k_rank_count)`` times of this thread under
+        ``PGB_WALK_TIMING=1`` in milliseconds (-1.0: none yet)."""
+        try:
+            f = self.lib.pgb_rank_kernel_ms
+        except AttributeError:
+            raise NotImplementedError(f"{self.path} does not export pgb_rank_kernel_ms (HIP library only)") from None
+        f.argtypes = [C.POINTER(C.c_double)] * 3
+        f.restype = C.c_int
+        ms = [C.c_double(), C.c_double(), C.c_double()]
+        self.check(f(*(C.byref(v) for v in ms)), "pgb_rank_kernel_ms")
+        return tuple(float(v.value) for v in ms)
+
     def hstat_entry_points(self):
         """``pgb_hstat_workspace_bytes``, ``pgb_hstat_background``, ``pgb_hstat_rows`` and ``pgb_hstat_finish``
         (include/pgbart_hstat.h): HIP library only, hence not in SYMBOLS.  A library without a symbol (the CPU

@@ -62,6 +62,7 @@
 #include "pgbart_hstat.h"
 #include "pgbart_arms.h"
 #include "pgbart_surv.h"
+#include "pgbart_rank.h"
 
 #include "pgb_dims.h"
 
@@ -99,3 +100,4 @@
 #include "k_hstat.h"
 #include "k_arms.h"
 #include "k_surv.h"
+#include "k_rank.h"

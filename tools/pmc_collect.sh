@@ -13,7 +13,8 @@ A="$A --no-extras --no-cpu-baseline --no-roofline --no-multichain --no-workloads
 DIRS=""
 for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU SQ_WAVES; do
   rm -rf /tmp/pmc_${W}_$C
-  rocprofv3 --pmc $C -d /tmp/pmc_${W}_$C --output-format csv -- python3 $R/bench.py $A > /dev/null 2> /tmp/pmc_${W}_$C.err || tail -3 /tmp/pmc_${W}_$C.err
+  # every pass under its own time limit; a pass that fails ends the script: nothing more is started on the GPU after it
+  timeout -k 10 ${PMC_PASS_SECONDS:-600} rocprofv3 --pmc $C -d /tmp/pmc_${W}_$C --output-format csv -- python3 $R/bench.py $A > /dev/null 2> /tmp/pmc_${W}_$C.err || { tail -3 /tmp/pmc_${W}_$C.err; exit 1; }
   DIRS="$DIRS /tmp/pmc_${W}_$C"
 done
 python3 $R/tools/pmc_summary.py --tail 0.15 $DIRS > /tmp/pmc_${W}.json

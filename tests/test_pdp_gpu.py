@@ -110,21 +110,26 @@ def test_one_pick(plain):
 
 
 # ------------------------------------------------------------------ 2. layout
-def _raw(hip, s, Xwide, p, cols, picks, route):
-    """``pgb_predict_pdp`` itself on a matrix whose rows are ``ldx = Xwide.shape[1] >= p`` apart."""
+def _raw(hip, s, Xwide, p, cols, picks, route, guard=None):
+    """``pgb_predict_pdp`` itself on a matrix whose rows are ``ldx = Xwide.shape[1] >= p`` apart.  ``guard``: 64 cells of
+    it lie behind the output and come back third."""
     mem, lib = hip.mem, hip.lib
     n, ldx = Xwide.shape
     cols, picks = np.ascontiguousarray(cols, np.int32), np.ascontiguousarray(picks, np.int32)
     K = s.n_outputs
     xd = mem.from_host(np.ascontiguousarray(Xwide))
-    od = mem.empty((cols.size * picks.shape[1] * K * n,), np.float64)
+    size = cols.size * picks.shape[1] * K * n
+    od = mem.empty((size,), np.float64) if guard is None else mem.from_host(np.full(size + 64, guard))
     rt = np.zeros(cols.size, np.int32)
     carr = s.pool.as_c()
     rc = lib.pdp_entry_point()(C.byref(carr), s.forest_idx.ctypes.data, s.n_draws, s.m, mem.ptr(xd), n, p, ldx,
                                cols.ctypes.data, cols.size, picks.ctypes.data, picks.shape[1], route, mem.ptr(od),
                                rt.ctypes.data, mem.stream_ptr)
     lib.check(rc, "pgb_predict_pdp")
-    return mem.to_host(od).reshape(cols.size, picks.shape[1], K, n), rt.tolist()
+    got = mem.to_host(od)
+    if guard is not None:
+        return got[:size].reshape(cols.size, picks.shape[1], K, n), rt.tolist(), got[size:]
+    return got.reshape(cols.size, picks.shape[1], K, n), rt.tolist()
 
 
 def test_rows_further_apart_than_p(plain, hip):

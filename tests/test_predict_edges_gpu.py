@@ -444,8 +444,10 @@ def test_arbitrary_pools_stay_within_the_derived_bound(case, hip, oracle):
 
 
 # ------------------------------------------------------------------ the other kernels of the walk at the same edges
-def pointwise(hip, pool, fidx, X, y, sigma, ldx=None):
-    """``pgb_pointwise_loglik`` (Normal family, matrix output) -> (D, n)."""
+def pointwise(hip, pool, fidx, X, y, sigma, ldx=None, family="normal", clamped=None):
+    """``pgb_pointwise_loglik`` (matrix output) -> (D, n).  ``sigma``: the Normal family's parameter per draw -- for
+    another built-in ``family`` its parameters ``(D, n_params)``.  ``clamped``: a list that takes the count of clamped
+    entries in place of the assertion that there is none."""
     X = np.ascontiguousarray(X, np.float64)
     n, p = X.shape
     fidx = np.ascontiguousarray(fidx, np.int32)
@@ -456,14 +458,19 @@ def pointwise(hip, pool, fidx, X, y, sigma, ldx=None):
     od = mem.from_host(np.full(D * n + 8, GUARD))
     sigma = np.ascontiguousarray(sigma, np.float64)
     lik = _abi.PointwiseLik()
-    lik.family, lik.n_params, lik.params_host, lik.y_dev = _abi.FAMILIES["normal"], 1, sigma.ctypes.data, mem.ptr(yd)
+    lik.family, lik.n_params, lik.y_dev = _abi.FAMILIES[family], sigma.size // D, mem.ptr(yd)
+    lik.params_host = sigma.ctypes.data if sigma.size else None
     carr = pool.as_c()
     nc = C.c_int64(0)
     rc = lib.pointwise_entry_point()(C.byref(carr), fidx.ctypes.data, D, m, mem.ptr(xd), n, p, a.shape[1], C.byref(lik),
                                      mem.ptr(od), None, C.byref(nc), mem.stream_ptr)
     lib.check(rc, "pgb_pointwise_loglik")
     out = mem.to_host(od)
-    assert np.all(out[D * n:] == GUARD) and nc.value == 0
+    assert np.all(out[D * n:] == GUARD)
+    if clamped is None:
+        assert nc.value == 0
+    else:
+        clamped.append(int(nc.value))
     return out[:D * n].reshape(D, n)
 
 

@@ -49,21 +49,26 @@ def _check(s, X, picks):
     return got, base
 
 
-def _raw(hip, pool, table, Xw, p, picks):
-    """The entry point itself on a matrix whose leading dimension exceeds ``p``: ``(n_picks, K, p, n)``."""
+def _raw(hip, pool, table, Xw, p, picks, guard=None):
+    """The entry point itself on a matrix whose leading dimension exceeds ``p``: ``(n_picks, K, p, n)``.  ``guard``:
+    64 cells of it lie behind the output and come back third."""
     mem, lib = hip.mem, hip.lib
     n, ldx = Xw.shape
     K = int(pool.n_outputs)
     fidx = np.ascontiguousarray(table, np.int32)
     picks = np.ascontiguousarray(picks, np.int32)
     xd = mem.from_host(np.ascontiguousarray(Xw))
-    od = mem.empty((picks.size * K * p * n,), np.float64)
+    size = picks.size * K * p * n
+    od = mem.empty((size,), np.float64) if guard is None else mem.from_host(np.full(size + 64, guard))
     base = np.empty((picks.size, K))
     carr = pool.as_c()
     rc = lib.shap_entry_point()(C.byref(carr), fidx.ctypes.data, fidx.shape[0], fidx.shape[1], mem.ptr(xd), n, p, ldx,
                                 picks.ctypes.data, picks.size, mem.ptr(od), base.ctypes.data, mem.stream_ptr)
     lib.check(rc, "pgb_predict_shap")
-    return mem.to_host(od).reshape(picks.size, K, p, n), base
+    got = mem.to_host(od)
+    if guard is not None:
+        return got[:size].reshape(picks.size, K, p, n), base, got[size:]
+    return got.reshape(picks.size, K, p, n), base
 
 
 def _data(rng, n, p, rules=None, nan_rate=0.08):

@@ -54,9 +54,10 @@ def _check(s, X, picks, cols=None):
     return got, base
 
 
-def _raw(hip, pool, table, Xw, p, cols, picks, fill=None):
+def _raw(hip, pool, table, Xw, p, cols, picks, fill=None, guard=None):
     """The entry point itself on a matrix whose leading dimension may exceed ``p``: ``(rc, (n_picks, K, q, q, n),
-    base)``; ``fill``: what the output holds before the call."""
+    base)``; ``fill``: what the output holds before the call; ``guard``: 64 cells of it lie behind the output and come
+    back fourth."""
     mem, lib = hip.mem, hip.lib
     n, ldx = Xw.shape
     K = int(pool.n_outputs)
@@ -67,12 +68,17 @@ def _raw(hip, pool, table, Xw, p, cols, picks, fill=None):
     xd = mem.from_host(np.ascontiguousarray(Xw))
     size = picks.size * K * q * q * n
     od = mem.empty((size,), np.float64) if fill is None else mem.from_host(np.full(size, fill))
+    if guard is not None:
+        od = mem.from_host(np.concatenate([np.full(size, guard if fill is None else fill), np.full(64, guard)]))
     base = np.empty((picks.size, K))
     carr = pool.as_c()
     rc = lib.shap_interactions_entry_point()(C.byref(carr), fidx.ctypes.data, fidx.shape[0], fidx.shape[1], mem.ptr(xd), n, p,
                                              ldx, cols.ctypes.data, q, picks.ctypes.data, picks.size, mem.ptr(od),
                                              base.ctypes.data, mem.stream_ptr)
-    return rc, mem.to_host(od).reshape(picks.size, K, q, q, n), base
+    got = mem.to_host(od)
+    if guard is not None:
+        return rc, got[:size].reshape(picks.size, K, q, q, n), base, got[size:]
+    return rc, got.reshape(picks.size, K, q, q, n), base
 
 
 def _data(rng, n, p, rules=None, nan_rate=0.08):

@@ -12,7 +12,14 @@ include/pgbart_image.h -- at random steps, and must still be the chain the oracl
 neighbouring doubles, beyond the float32 range, subnormals, -inf .. +inf -- by draws of their own, made after the
 configuration's; the HIP chain on the recoded data must be the oracle's there AND, but for the split values, the HIP
 chain on the data as drawn.  Constant leaves only: the seeds of linear / mix configurations are skipped.  Run it with
-PGB_X32_MIN_MB=0 as well: the order keys of such columns)"""
+PGB_X32_MIN_MB=0 as well: the order keys of such columns)
+
+usage: python tools/fuzz_hunt.py FIRST_SEED COUNT [SECONDS] --stored [ENTRY ...]
+(--stored: the stored-draw entry points instead of the sampler -- tests/_stored_fuzz.random_walk_case draws a pool, a
+forest table, rows and every argument of a call at once; each ENTRY of _stored_fuzz.RUNNERS, default all of them, lays
+the device call out as its GPU module does and holds it to its host reference: bit for bit, guard cells, padding,
+identities.  The same MISMATCH and summary lines and the same exit status; the counts are by (entry point, p at or
+below / above PRED_LDS_MAXP, rules, K).  A GPU error ends the hunt: nothing is started after it.)"""
 import os
 import sys
 import time
@@ -27,6 +34,39 @@ from pymc_bart_amd.sampler import default_backend  # noqa: E402
 
 first, count = int(sys.argv[1]), int(sys.argv[2])
 budget = float(sys.argv[3]) if len(sys.argv) > 3 and not sys.argv[3].startswith("--") else 1e9
+
+
+def hunt_stored(entries) -> int:
+    import _stored_fuzz as F
+
+    unknown = [e for e in entries if e not in F.RUNNERS]
+    if unknown:
+        sys.exit(f"no such entry point: {unknown}; the runners are {sorted(F.RUNNERS)}")
+    entries = entries or sorted(F.RUNNERS)
+    hip, orc = default_backend(0), oracle_backend()
+    t0, bad, done, runs, by = time.time(), [], 0, 0, {}
+    for seed in range(first, first + count):
+        if time.time() - t0 > budget:
+            break
+        c = F.random_walk_case(seed, orc)
+        for entry in entries:
+            diff = F.check(entry, c, hip, orc)  # (a GPU error is no AssertionError: it ends the hunt here)
+            key = (entry, "p > LDS" if c["p"] > F.LDS_MAXP else "p <= LDS", c["took"]["rules"], c["K"])
+            by[key] = by.get(key, 0) + 1
+            runs += 1
+            if diff:
+                bad.append((seed, entry))
+                print("MISMATCH", seed, entry, "; ".join(diff), "|", F.describe(c), flush=True)
+        done += 1
+    dt = time.time() - t0
+    print(f"fuzz: seeds {first}..{first + done - 1}: {done} configurations, {len(bad)} mismatches {bad}, {dt:.0f} s")
+    print(f"stored: {runs} runs of {len(entries)} entry points, {runs / max(dt, 1e-9):.2f} per second")
+    print("by (entry point, p, rules, K):", sorted(by.items(), key=lambda kv: -kv[1]))  # (every class: the rare ones matter)
+    return 1 if bad else 0
+
+
+if "--stored" in sys.argv[3:]:
+    sys.exit(hunt_stored(sys.argv[sys.argv.index("--stored") + 1:]))
 large = "large" in sys.argv[4:]
 compat_on = "compat" in sys.argv[4:]
 mk_only = "mk" in sys.argv[4:]
